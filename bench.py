@@ -13,8 +13,14 @@ own batch shard (the path shards by sample; inference has no collective), so sca
 ``--global-batch G`` fixes the total batch instead (G / N per GPU, "scaling": "strong"), e.g. the
 C4 training config: ``--workload egno_train --global-batch 4096``.
 
-The CPU baseline is oracle/torch_ref.py — the reference's own torch operators, op by op, on the
-host cores — and the HIP outputs are checked against it on the same batch.
+A plain run does only what the headline figure needs: set-up, the clock-ramp calls and the W warmup
+steps, the K timed steps, then the JSON line. ``--dump-outputs DIR`` also writes what the last timed
+step returned (dump_outputs). ``--full`` adds everything else the bench measures or checks, each in
+a pass of its own after the timed steps: per-kernel durations and the roofline, the host overhead
+per forward, the CPU baseline with the parity check against it, and the rocm-smi clocks in "device".
+
+The CPU baseline (--full) is oracle/torch_ref.py — the reference's own torch operators, op by op, on
+the host cores — and the HIP outputs are checked against it on the same batch.
 """
 import argparse
 import json
@@ -161,14 +167,17 @@ def _prewarm(call, args, dev):
             break
 
 
-def device_info(dev):
-    """What the run ran on: CU count (the layer kernels size their grid by it), arch, clocks and
-    partition modes (rocm-smi, best effort) — to tell box-to-box variance from code changes."""
+def device_info(dev, smi=True):
+    """What the run ran on: CU count (the layer kernels size their grid by it), arch, and with `smi`
+    (--full) clocks and partition modes (rocm-smi, best effort) — to tell box-to-box variance from
+    code changes."""
     if dev.type != "cuda":
         return None
     p = torch.cuda.get_device_properties(dev)
     info = {"name": p.name, "arch": getattr(p, "gcnArchName", None), "cus": p.multi_processor_count,
             "hbm_gib": round(p.total_memory / 2 ** 30, 1)}
+    if not smi:
+        return info
     if "rocprof" in os.environ.get("LD_PRELOAD", ""):
         # under rocprofv3 every child process carries its preload (which initialises the GPU) and
         # rocm-smi is a script that re-execs its interpreter: skip it there
@@ -184,6 +193,30 @@ def device_info(dev):
     except Exception as e:   # noqa: BLE001 - informational only
         info["smi"] = f"unavailable ({type(e).__name__})"
     return info
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(args, rank, arrays):
+    """--dump-outputs DIR: write what the last timed step returned as DIR/<name>.npy (float64 outputs
+    as float64, everything else as float32; ranks above 0 write DIR/<name>.rank<r>.npy), to compare
+    two builds output for output: the inputs are seeded, so they are the same from run to run. The
+    files hold at most DUMP_BUDGET_BYTES in all, an equal share per array; a larger array is written
+    as a fixed sample of its flattened elements (default_rng(0) indices, sorted, the same every run)."""
+    if not args.dump_outputs:
+        return
+    arrays = {k: t.detach() for k, t in arrays.items() if t is not None}
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    for name, t in arrays.items():
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        keep = share // t.element_size()
+        if t.numel() > keep:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), keep))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        suffix = f".rank{rank}" if rank else ""
+        np.save(os.path.join(args.dump_outputs, f"{name}{suffix}.npy"), t.cpu().numpy())
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -391,6 +424,7 @@ def run_egno(args, world, rank, dev, backend):
             out = call()
         barrier_sync(world, dev)
         el = time.perf_counter() - t0
+        dump_outputs(args, rank, dict(zip(("x", "v", "h"), out)))
         # kernel durations for the roofline: a separate instrumented pass over the same workload
         # (hipEvents recorded around every launch on its stream; kept out of the timed loop above)
         records = []
@@ -402,7 +436,7 @@ def run_egno(args, world, rank, dev, backend):
         # host overhead per forward: with an idle GPU before each call, the host time
         # to enqueue one forward and its synchronous wall time, against the recorded kernel time
         enq, wall = [], []
-        for _ in range(10):
+        for _ in range(10 if args.full else 0):
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
             out = call()
@@ -419,13 +453,14 @@ def run_egno(args, world, rank, dev, backend):
                    "parallelism": f"batch-sharded replicas x{world} (no collective)"}, backend,
                   frames_per_s=value * T)
     kern_ms = float(np.sum([ms for _, ms in records])) / args.steps if records else None
-    res["host_overhead"] = {
-        "enqueue_ms_median": float(np.median(enq)) * 1e3, "sync_wall_ms_median": float(np.median(wall)) * 1e3,
-        "recorded_kernel_ms_per_call": kern_ms,
-        "note": "per forward with an idle GPU before the call: enqueue = host time until the call returns; "
-                "sync_wall = until its kernels finish; recorded kernels = the layer and TimeConv launches "
-                "(hipEvents, temb_kernel not recorded). ms_per_step is the pipelined rate (host enqueues "
-                "ahead of the GPU)"}
+    if enq:
+        res["host_overhead"] = {
+            "enqueue_ms_median": float(np.median(enq)) * 1e3, "sync_wall_ms_median": float(np.median(wall)) * 1e3,
+            "recorded_kernel_ms_per_call": kern_ms,
+            "note": "per forward with an idle GPU before the call: enqueue = host time until the call returns; "
+                    "sync_wall = until its kernels finish; recorded kernels = the layer and TimeConv launches "
+                    "(hipEvents, temb_kernel not recorded). ms_per_step is the pipelined rate (host enqueues "
+                    "ahead of the GPU)"}
     layer_events = [ms for kind, ms in records if kind == _lib.VARIANT_EGNO]
     tconv_ms = [ms for kind, ms in records if kind in (_lib.PROF_TCONV, _lib.PROF_TCONV_FIRST)]
     if layer_events:
@@ -506,6 +541,7 @@ def run_segno(args, world, rank, dev, backend, gravity=False):
             out = call()
         barrier_sync(world, dev)
         el = time.perf_counter() - t0
+        dump_outputs(args, rank, {"x": out})
         records = []
         if args.kernel_events:
             _lib.profile_begin(8 * args.steps * len(steps) + 64)
@@ -580,6 +616,14 @@ def make_adam(args, params, **kw):
     return torch.optim.Adam(params, fused=args.optimizer == "fused", foreach=args.optimizer == "foreach", **kw)
 
 
+def _train_outputs(loss, model):
+    """What a training step leaves its caller (dump_outputs): the loss, the gradients the optimizer
+    stepped on and the parameters after the step, each flattened in named_parameters() order."""
+    ps = [p for p in model.parameters() if p.requires_grad]
+    grads = [(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in ps]
+    return {"loss": loss, "grads": torch.cat(grads), "params": torch.cat([p.detach().reshape(-1) for p in ps])}
+
+
 def run_egno_train(args, world, rank, dev, backend):
     """C4: EGNO training step, charged N=20, T=10, B=512 per GPU (or --global-batch 4096 over the
     ranks): forward with saved state, the reference loss (main_simulation_simple_no.py:273-280),
@@ -637,6 +681,7 @@ def run_egno_train(args, world, rank, dev, backend):
         loss = step()
     barrier_sync(world, dev)
     el = max_over_ranks(time.perf_counter() - t0, dev)
+    dump_outputs(args, rank, _train_outputs(loss, model))
     records = []
     if args.kernel_events:
         _lib.profile_begin(64 * args.steps + 64)
@@ -789,9 +834,10 @@ def run_segno_train(args, world, rank, dev, backend):
     barrier_sync(world, dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        loss = step()
     barrier_sync(world, dev)
     el = max_over_ranks(time.perf_counter() - t0, dev)
+    dump_outputs(args, rank, _train_outputs(loss, model))
     records = []
     if args.kernel_events:
         _lib.profile_begin(64 * args.steps * T + 64)
@@ -897,6 +943,7 @@ def run_egno_rollout(args, world, rank, dev, backend):
         out = call()
     barrier_sync(world, dev)
     el = max_over_ranks(time.perf_counter() - t0, dev)
+    dump_outputs(args, rank, dict(zip(("preds", "energy", "energy_all"), out)))
     records = []
     if args.kernel_events:
         _lib.profile_begin(16 * L * 2 + 64)
@@ -986,6 +1033,7 @@ def run_sim_charged(args, world, rank, dev, backend):
     el = time.perf_counter() - t0
     records = _lib.profile_end() if args.kernel_events else []
     el = max_over_ranks(el, dev)
+    dump_outputs(args, rank, {"loc": out[0], "vel": out[1]})
     value = plan["B_global"] * args.steps / el
     res = _result(args, world, plan, el / args.steps * 1e3, value,
                   f"f3: ChargedParticlesSim N={N}, length {Tn}, sample_freq {freq}, S={S} per GPU",
@@ -1060,7 +1108,12 @@ def parse_args(argv=None):
                     choices=["egno", "segno", "segno_gravity", "egno_train", "segno_train", "egno_rollout", "sim_charged"],
                     help="egno = C2 (the headline line); segno = C3; segno_gravity = C5; egno_train = C4; "
                          "egno_rollout = SURVEY row f1; sim_charged = row f3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else: per-kernel durations and "
+                         "the roofline, host overhead, the CPU baseline and parity against it, rocm-smi clocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity")
     ap.add_argument("--no-grad-parity", action="store_true", help="skip the C4 whole-batch gradient parity check")
     ap.add_argument("--edges", choices=["fixed", "get_edges", "fresh"], default="fixed",
                     help="C2: the edge tensors each step gets (run_egno.edges)")
@@ -1070,11 +1123,16 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-samples", type=int, default=0, help="CPU baseline sample size where it is bounded")
     ap.add_argument("--prewarm-ms", type=float, default=300.0,
                     help="untimed clock-ramp calls (wall ms) before the W warmup steps")
-    ap.add_argument("--no-kernel-events", dest="kernel_events", action="store_false")
+    ap.add_argument("--no-kernel-events", dest="kernel_events", action="store_false",
+                    help="with --full: skip the instrumented pass (no roofline)")
     ap.add_argument("--check-launch", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:   # a plain run: the timed steps only
+        args.kernel_events, args.no_cpu_baseline = False, True
     if args.global_batch and args.global_batch < args.gpus:
         ap.error("--global-batch must be >= --gpus")
     return args
@@ -1093,8 +1151,9 @@ def main():
                    "segno_gravity": lambda *a: run_segno(*a, gravity=True)}
         res = runners[args.workload](args, world, rank, dev, backend)
         if rank == 0:
+            res["full"] = args.full
             res["prewarm_ms"] = args.prewarm_ms
-            res["device"] = device_info(dev)
+            res["device"] = device_info(dev, smi=args.full)
     if rank == 0:
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -57,6 +57,49 @@ def test_strong_scaling_plan():
     assert p["B"] == 512 and p["B_global"] == 2048 and p["scaling"] == "weak"
 
 
+def test_plain_run_is_lean_and_full_restores_the_extras():
+    """Without --full nothing but the timed steps runs (no instrumented pass, no CPU baseline);
+    --full turns both back on, and its --no-* options still narrow it."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.kernel_events, a.no_cpu_baseline, a.dump_outputs) == (False, False, True, None)
+    assert (a.steps, a.warmup) == (7, 2)
+    a = bench.parse_args(["--full"])
+    assert (a.full, a.kernel_events, a.no_cpu_baseline) == (True, True, False)
+    a = bench.parse_args(["--full", "--no-cpu-baseline", "--no-kernel-events"])
+    assert (a.full, a.kernel_events, a.no_cpu_baseline) == (True, False, True)
+
+
+def test_dump_outputs_writes_seeded_bounded_arrays(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, the same from call to call, a fixed sample of an
+    array over its share of the byte budget, nothing written without the option."""
+    import types
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    big = torch.randn(bench.DUMP_BUDGET_BYTES // 4 // 3 + 1000, generator=g)    # over a third of the budget
+    arrays = {"x": torch.randn(7, 3, generator=g), "e": torch.randn(5, generator=g).double(), "big": big,
+              "none": None}
+    bench.dump_outputs(types.SimpleNamespace(dump_outputs=None), 0, arrays)
+    assert not list(tmp_path.iterdir())
+    for d in ("a", "b"):
+        bench.dump_outputs(types.SimpleNamespace(dump_outputs=str(tmp_path / d)), 0, arrays)
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["big.npy", "e.npy", "x.npy"]
+    assert got["x.npy"].dtype == np.float32 and np.array_equal(got["x.npy"], arrays["x"].numpy())
+    assert got["e.npy"].dtype == np.float64 and np.array_equal(got["e.npy"], arrays["e"].numpy())
+    assert got["big.npy"].shape == (bench.DUMP_BUDGET_BYTES // 3 // 4,)
+    assert np.isin(got["big.npy"], big.numpy()).all()
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_BUDGET_BYTES
+    assert all(np.array_equal(a, np.load(tmp_path / "b" / f)) for f, a in got.items())
+    bench.dump_outputs(types.SimpleNamespace(dump_outputs=str(tmp_path / "a")), 2, {"x": arrays["x"]})
+    assert os.path.exists(tmp_path / "a" / "x.rank2.npy")
+
+
 def test_every_workload_is_registered():
     """Each --workload choice parses (row †g's segno_train included)."""
     sys.path.insert(0, ROOT)

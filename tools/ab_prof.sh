@@ -8,7 +8,7 @@ for rep in $(seq ${REPS:-1}); do
   for n in $LIBS; do
     out=gpurun_out/abprof_${n}_$rep
     NONODE_LIB=$PWD/ab/lib_$n.so timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o run -- \
-      python3 bench.py --workload ${WL:-egno} --steps 10 --warmup 2 --no-cpu-baseline ${ARGS:-} > $out.json 2> $out.err \
+      python3 bench.py --workload ${WL:-egno} --steps 10 --warmup 2 --full --no-cpu-baseline ${ARGS:-} > $out.json 2> $out.err \
       || { echo "fail $n"; tail -3 $out.err; exit 1; }
     python3 - "$out/run_kernel_stats.csv" "$n" "${KPAT:-tconv}" <<'PY'
 import csv, sys

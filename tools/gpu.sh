@@ -5,7 +5,7 @@
 # time-out or failed bench, and pytest failures (rc 1) stop it unless KEEP_GOING=1):
 #   tests    pytest -m gpu over $TESTS (default tests/), measured-parity report in $O/parity_report.json
 #   smoke    __graft_entry__.smoke()
-#   bench    one plain bench line per spec in $BENCH ("name:bench args", default: the C2 headline)
+#   bench    one bench line (bench.py --full) per spec in $BENCH ("name:bench args", default: the C2 headline)
 #   ab       same-box A/B of library builds ab/lib_<name>.so ($LIBS) over $WLS (workload:steps:warmup),
 #            alternating $REPS times; prints step ms and the workload's roofline-kernel launch us
 #   profile  rocprofv3 --kernel-trace --stats of $WORKLOADS, then FETCH_SIZE / WRITE_SIZE passes (one
@@ -41,7 +41,7 @@ step_bench() {
   while IFS= read -r spec; do
     [ -z "$spec" ] && continue
     name=${spec%%:*}; args=${spec#*:}
-    timeout -k 10 400 python -u bench.py $args > $O/bench_$name.json 2> $O/bench_$name.err
+    timeout -k 10 400 python -u bench.py --full $args > $O/bench_$name.json 2> $O/bench_$name.err
     local rc=$?; [ $rc -ne 0 ] && { echo "bench $name rc=$rc"; tail -5 $O/bench_$name.err; exit $rc; }
     echo "bench $name: $(jget $O/bench_$name.json "round(d['value']), d['unit'], 'ms', round(d['ms_per_step'], 4), 'kernel_us', round((r.get('avg_launch_ms') or 0) * 1e3, 1), 'frac', r.get('frac') and round(r['frac'], 4)")"
   done <<< "${BENCH:-egno:}"
@@ -56,7 +56,7 @@ step_ab() {
         IFS=: read -r wl st wu <<< "$spec"
         f=$O/ab_${n}_$wl.json
         NONODE_LIB=$PWD/ab/lib_$n.so timeout -k 10 240 python3 bench.py --workload $wl --steps $st --warmup $wu \
-          --no-cpu-baseline ${AB_ARGS:-} > $f 2> $O/ab_${n}_$wl.err || { echo "fail $n $wl"; tail -3 $O/ab_${n}_$wl.err; exit 1; }
+          --full --no-cpu-baseline ${AB_ARGS:-} > $f 2> $O/ab_${n}_$wl.err || { echo "fail $n $wl"; tail -3 $O/ab_${n}_$wl.err; exit 1; }
         line="$line $wl=$(jget $f "round(d['ms_per_step'], 4), round((r.get('avg_launch_ms') or 0) * 1e3, 1), [round(x * 1e3, 1) for x in r.get('pass_ms', [])]")"
       done
       echo "$line"
@@ -70,7 +70,7 @@ step_profile() {
     OUT=gpurun_out/prof_${TAG:-r04}_$wl
     mkdir -p $OUT
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py \
-      --workload $wl --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/trace.err
+      --workload $wl --steps 10 --warmup 2 --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/trace.err
     local rc=$?; echo "trace $wl rc=$rc"; [ $rc -ne 0 ] && { tail -3 $OUT/trace.err; exit $rc; }
   done
   # PMC: "name:bench args" specs separated by '|', e.g. PMC="c5:--workload segno_gravity|c4_4096:--workload

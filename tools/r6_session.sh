@@ -10,7 +10,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo smoke fail; tail -5 $O/smoke.log; exit 1; }
   tail -1 $O/smoke.log
 fi
-BENCHES=${BENCHES:-"egno:--steps 20|b256:--batch 256 --steps 30 --no-cpu-baseline|b128:--batch 128 --steps 40 --no-cpu-baseline|b64:--batch 64 --steps 50 --no-cpu-baseline"}
+BENCHES=${BENCHES:-"egno:--full --steps 20|b256:--full --batch 256 --steps 30 --no-cpu-baseline|b128:--full --batch 128 --steps 40 --no-cpu-baseline|b64:--full --batch 64 --steps 50 --no-cpu-baseline"}
 IFS='|' read -ra specs <<< "$BENCHES"
 for spec in "${specs[@]}"; do
   name=${spec%%:*}; args=${spec#*:}
