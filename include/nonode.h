@@ -294,6 +294,37 @@ int nonode_egno_backward_frames(int B, int N, int T, int n_layers, int in_node, 
                                 size_t workspace_bytes, void* stream);
 
 /*
+ * Input gradients of EGNO.forward (egno.py:37-111: x.repeat / v.repeat :89-96, the embedding Linear
+ * :63-76, x - loc_mean ... + loc_mean :103-107). Frame t of the forward read input slot
+ * frame_input[t] (host array [T]; NULL = every frame reads slot 0, which n_inputs == 1 requires; the
+ * multi-input model's repeat_elements_to_exact_shape map otherwise). Device outputs, each may be NULL
+ * (not computed), written not accumulated, sums over the frames of a slot in frame order:
+ * g_x_in, g_v_in, g_loc_mean [n_inputs][B*N][3], g_h_in [n_inputs][B*N][in_node]. g_h_in needs emb_w
+ * (the embedding weight [64][in_node + time-embedding columns] the forward used); g_loc_mean needs
+ * time convolutions (without them the forward does not read loc_mean).
+ */
+typedef struct {
+  int n_inputs;
+  const int* frame_input;
+  const float* emb_w;
+  float* g_x_in;
+  float* g_v_in;
+  float* g_h_in;
+  float* g_loc_mean;
+} nonode_input_grads;
+
+/* nonode_egno_backward (frames = 0; with_t_in ignored) or nonode_egno_backward_frames (frames = 1)
+ * that also writes the input gradients *inputs asks for. Same workspace size. With inputs NULL or all
+ * four of its outputs NULL it issues exactly the launches of those two entries. */
+int nonode_egno_backward_inputs(int frames, int B, int N, int T, int n_layers, int in_node, int n_edge_feat,
+                                int time_emb_dim, int with_t_in, int modes, int Bt, const float* loc_mean,
+                                const float* edge_fea, const float* const* bblobs, const float* const* tconv_w,
+                                const float* const* tconvx_w, const void* state, const float* g_x, const float* g_v,
+                                const float* g_h, const nonode_layer_grads* layer_grads, float* const* g_tconv,
+                                float* const* g_tconvx, float* g_emb_w, float* g_emb_b, void* workspace,
+                                size_t workspace_bytes, void* stream, const nonode_input_grads* inputs);
+
+/*
  * SEGNO training (replaces loss.backward() of SEGNO/train_nbody.py:168-179 through forward_step,
  * SEGNO/models/model.py:95-102, = T applications of SEGNO_GCL.forward, gcl.py:111-119, dt = 1/T).
  * nonode_segno_forward_train: forward_step from an embedded h [B*N][64] (the caller's embedding
@@ -377,6 +408,14 @@ int nonode_egno_tconv_bwd(int BN, int T, int modes, const float* h, const float*
 int nonode_prepare_inputs(int B, int N, int F, const float* loc, const float* vel, const int* t_in,
                           const float* charges, const float* edge_attr_o, int n_eo, float* x_out,
                           float* v_out, float* nodes, float* edge_attr, float* loc_mean, void* stream);
+
+/* Reverse of nonode_prepare_inputs for what the reference keeps on the autograd tape (x_out, v_out and
+ * loc_mean; nodes and edge_attr are detached, main_simulation_simple_no.py:321-338). Given g_x, g_v,
+ * g_lm [B*N][3] (each may be NULL = 0) writes g_loc, g_vel [F][B*N][3] (each may be NULL):
+ * g_loc[f_b][b][n] = g_x[b][n] + (1/N) sum_m g_lm[b][m], g_vel[f_b][b][n] = g_v[b][n], zero in every
+ * other frame (f_b as in nonode_prepare_inputs). */
+int nonode_prepare_inputs_bwd(int B, int N, int F, const int* t_in, const float* g_x, const float* g_v,
+                              const float* g_lm, float* g_loc, float* g_vel, void* stream);
 
 /* conserved_energy_fun (utils.py:197-219) of F frames x B graphs: loc, vel [F][B*N][3], weights [B*N]
  * (charges for kind 0 = charged, tot_energy_charged_batch utils.py:126-144; masses for kind 1 =

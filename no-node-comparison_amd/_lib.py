@@ -36,6 +36,7 @@ SYMBOLS = (
     "nonode_egnn_layer_flat_state_floats", "nonode_egnn_layer_flat", "nonode_flat_bwd_blob_floats",
     "nonode_pack_layer_flat_bwd", "nonode_egnn_layer_flat_bwd_node_floats", "nonode_egnn_layer_flat_bwd_edge_floats",
     "nonode_egnn_layer_flat_bwd",
+    "nonode_egno_backward_inputs", "nonode_prepare_inputs_bwd",
 )
 
 VARIANT_EGNO = 0
@@ -66,6 +67,12 @@ class LayerWeights(ctypes.Structure):
 class LayerGrads(ctypes.Structure):
     """nonode_layer_grads (same fields as LayerWeights, written by nonode_egno_backward)."""
     _fields_ = LayerWeights._fields_
+
+
+class InputGrads(ctypes.Structure):
+    """nonode_input_grads (nonode_egno_backward_inputs)."""
+    _fields_ = [("n_inputs", _i), ("frame_input", ctypes.POINTER(_i)), ("emb_w", _vp), ("g_x_in", _vp),
+                ("g_v_in", _vp), ("g_h_in", _vp), ("g_loc_mean", _vp)]
 
 
 _lib = None
@@ -164,6 +171,8 @@ def lib():
     L.nonode_egno_backward_frames.argtypes = ([_i] * 10 + [_vp] * 2 + [ctypes.POINTER(_vp)] * 3 + [_vp] * 4
                                               + [ctypes.POINTER(LayerGrads), ctypes.POINTER(_vp),
                                                  ctypes.POINTER(_vp)] + [_vp] * 3 + [_sz, _vp])
+    L.nonode_egno_backward_inputs.argtypes = ([_i] + L.nonode_egno_backward_frames.argtypes
+                                              + [ctypes.POINTER(InputGrads)])
     L.nonode_egno_backward_workspace_bytes.argtypes = [_i] * 4
     L.nonode_egno_backward_workspace_bytes.restype = _sz
     L.nonode_egno_backward.argtypes = ([_i] * 9 + [_vp] * 2 + [ctypes.POINTER(_vp)] * 3 + [_vp] * 4
@@ -188,6 +197,7 @@ def lib():
     L.nonode_egno_tconv_bwd_workspace_bytes.restype = _sz
     L.nonode_egno_tconv_bwd.argtypes = [_i] * 3 + [_vp] * 16 + [_sz, _vp]
     L.nonode_prepare_inputs.argtypes = [_i, _i, _i] + [_vp] * 5 + [_i] + [_vp] * 6
+    L.nonode_prepare_inputs_bwd.argtypes = [_i, _i, _i] + [_vp] * 7
     L.nonode_energy.argtypes = [_i] * 4 + [_vp] * 5
     L.nonode_egno_rollout_workspace_bytes.argtypes = [_i] * 6
     L.nonode_egno_rollout_workspace_bytes.restype = _sz

@@ -4,6 +4,9 @@ EGNOTrain is a torch.autograd.Function around the C ABI: its forward runs
 nonode_egno_forward_train (same kernels and outputs as the inference forward, plus the saved
 state), its backward runs nonode_egno_backward and returns the gradient of every parameter. The
 reference's training loop (criterion, loss.backward(), optimizer.step()) runs unchanged on top.
+Where x, v, h or loc_mean requires grad, the backward runs nonode_egno_backward_inputs instead (the
+same launches plus the input-gradient kernels) and returns those gradients too, as the reference's
+plain-torch forward does; edge_fea gets none (EGNO.forward refuses an edge_fea that requires grad).
 """
 import ctypes
 
@@ -18,12 +21,23 @@ def _f32(t):
 
 class EGNOTrain(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, x, h, edge_fea, v, loc_mean, t_out, t_in, B, N, *params):
+    def forward(ctx, model, x, h, edge_fea, v, loc_mean, t_out, t_in, B, N, slots, *params):
         # t_in is None for a single input; else the inputs are per frame (num_inputs > 1) and t_in
         # [Bt, T] is each frame's input time (nonode_egno_forward_train_frames)
+        # slots (multi-input, EGNO._forward_multi): x, h, v, loc_mean are the caller's [I, BN, .] tensors
+        # (the tape's inputs, so their gradients come back per slot) and slots = (frame -> slot map,
+        # (x, h, v, loc_mean) spread to the frames [T*BN, .]), which the kernels read
         L = _lib.lib()
         T = model.num_timesteps
         dev = x.device
+        ctx.in_dtypes = tuple(t.dtype if t is not None else None for t in (x, h, v, loc_mean))
+        ctx.in_shapes = tuple(t.shape if t is not None else None for t in (x, h, v, loc_mean))
+        if slots is not None:
+            ctx.frame_input, (x, h, v, loc_mean) = list(slots[0]), slots[1]
+            ctx.n_inputs = ctx.in_shapes[0][0]
+        else:   # one input, or (t_in without slots) one input per frame
+            ctx.n_inputs = 1 if t_in is None else T
+            ctx.frame_input = [0] * T if t_in is None else list(range(T))
         x, h, v, ef = _f32(x), _f32(h), _f32(v), _f32(edge_fea)
         tt = model._t_out_f32(t_out)   # cached per tensor / version: no int64 -> f32 copy per step
         lm = _f32(loc_mean) if loc_mean is not None else None   # unused without time convolutions
@@ -57,6 +71,7 @@ class EGNOTrain(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.model, ctx.B, ctx.N, ctx.Bt = model, B, N, Bt
         ctx.state, ctx.lm, ctx.ef = state, lm, ef
+        ctx.ew = ew
         ctx.n_params = len(params)
         sink = getattr(model, "_train_state_sink", None)
         if sink is not None:   # tests: the saved state (its head holds TimeConv's LeakyReLU decisions)
@@ -101,20 +116,36 @@ class EGNOTrain(torch.autograd.Function):
                 _lib.ptr(gx), _lib.ptr(gv), _lib.ptr(gh), lg, g_tc, g_tcx,
                 _lib.ptr(grads["embedding.weight"]), _lib.ptr(grads["embedding.bias"]), _lib.ptr(ws), ws_bytes,
                 _lib.stream_of(gx))
-        if ctx.frames:
+        # input gradients (x, h, v, loc_mean: arguments 1, 2, 4, 5), per input slot [n_inputs, BN, .]
+        want_x, want_h, want_v, want_lm = (ctx.needs_input_grad[k] for k in (1, 2, 4, 5))
+        want_lm = want_lm and ctx.lm is not None and model.use_time_conv   # else the forward did not read it
+        want_h = want_h and model.in_node_nf > 0
+        g_in = [None] * 4
+        if want_x or want_h or want_v or want_lm:
+            I, BN = ctx.n_inputs, B * N
+            new = lambda want, k: torch.empty(I, BN, k, device=dev) if want else None  # noqa: E731
+            g_in = [new(want_x, 3), new(want_h, model.in_node_nf), new(want_v, 3), new(want_lm, 3)]
+            fi = (ctypes.c_int * T)(*ctx.frame_input)
+            ig = _lib.InputGrads(I, fi, _lib.ptr(ctx.ew), _lib.ptr(g_in[0]), _lib.ptr(g_in[2]), _lib.ptr(g_in[1]),
+                                 _lib.ptr(g_in[3]))
+            _lib.check(L.nonode_egno_backward_inputs(int(ctx.frames), *head, 1, *tail, ctypes.byref(ig)))
+            g_in = [g.reshape(shp).to(dt) if g is not None else None
+                    for g, shp, dt in zip(g_in, ctx.in_shapes, ctx.in_dtypes)]
+        elif ctx.frames:
             _lib.check(L.nonode_egno_backward_frames(*head, 1, *tail))
         else:
             _lib.check(L.nonode_egno_backward(*head, *tail))
         ctx.state = None
         out = [grads[name] for name, _ in model.named_parameters()]
-        return (None,) * 10 + tuple(out)
+        g_x, g_h, g_v, g_lm = g_in
+        return (None, g_x, g_h, None, g_v, g_lm) + (None,) * 5 + tuple(out)
 
 
-def egno_forward_train(model, x, h, edge_fea, v, loc_mean, t_out, B, N, t_in=None):
+def egno_forward_train(model, x, h, edge_fea, v, loc_mean, t_out, B, N, t_in=None, slots=None):
     """EGNO forward that records the kernels' backward on the autograd tape (t_in: per-frame
-    multi-input form, see EGNO._forward_multi)."""
+    multi-input form, see EGNO._forward_multi; slots: see EGNOTrain.forward)."""
     params = [p for _, p in model.named_parameters()]
-    return EGNOTrain.apply(model, x, h, edge_fea, v, loc_mean, t_out, t_in, B, N, *params)
+    return EGNOTrain.apply(model, x, h, edge_fea, v, loc_mean, t_out, t_in, B, N, slots, *params)
 
 
 def _segno_forward(ctx, model, h, x, v, edge_attr, T, B, N):
@@ -257,6 +288,29 @@ def _flat_layer_params(model, i):
             v[0].weight, v[0].bias, v[2].weight, v[2].bias, n[0].weight, n[0].bias, n[2].weight, n[2].bias]
 
 
+def _tconvx_lm_grad(gxo, gvo, txw, T, modes):
+    """dL/dloc_mean [BN, 3] of one layer's x - loc_mean; TimeConv_x; + loc_mean (egno.py:103-107) from the
+    gradients gxo, gvo [T*BN, 3] of TimeConv_x's outputs: the identity parts cancel, leaving minus the
+    adjoint of the spectral term on the x channel summed over the frames (torch ops, the formula of
+    input_lm_grad_kernel in csrc/nonode_train.hip)."""
+    import math
+    M = min(modes, T // 2 + 1)
+    dev = gxo.device
+    G = torch.stack([gxo, gvo], -1).reshape(T, -1, 2)                      # [T, BN*3, channel o]
+    m = torch.arange(M, dtype=torch.float64, device=dev)
+    ang = 2 * math.pi * m[:, None] * torch.arange(T, dtype=torch.float64, device=dev)[None] / T
+    cm = torch.where((m == 0) | (2 * m == T), 1.0, 2.0) / T
+    C, S = torch.cos(ang).to(G.dtype), torch.sin(ang).to(G.dtype)           # [M, T]
+    cm = cm.to(G.dtype)[:, None]
+    gYr = torch.einsum("mt,tno->mno", cm * C, G)
+    gYi = -torch.einsum("mt,tno->mno", cm * S, G)
+    wr, wi = txw[0, :, :M, 0].t()[:, None], txw[0, :, :M, 1].t()[:, None]   # input channel 0: [M, 1, o]
+    gxr = (gYr * wr + gYi * wi).sum(-1)                                     # [M, BN*3]
+    gxi = (-gYr * wi + gYi * wr).sum(-1)
+    spec = (gxr * C.sum(1)[:, None] - gxi * S.sum(1)[:, None]).sum(0)
+    return -spec.reshape(-1, 3)
+
+
 class FlatLayerTrain(torch.autograd.Function):
     """TimeConv (+ TimeConv_x) of layer i, then its flat EGNN layer (egno.py:99-111 with flat=True)."""
 
@@ -351,7 +405,8 @@ class FlatLayerTrain(torch.autograd.Function):
         sink = getattr(model, "_train_bwd_sink", None)
         if sink is not None:   # tests: the workspace head holds the LeakyReLU decisions the reverse used
             sink.append((i, ws))
-        return (None,) * 4 + (g_h, g_x, g_v, None, None) + tuple(grads) + (g_tw.to(params[16].dtype),
+        g_lm = _tconvx_lm_grad(gxt, gvt, txw, T, model.num_modes) if ctx.needs_input_grad[7] else None
+        return (None,) * 4 + (g_h, g_x, g_v, g_lm, None) + tuple(grads) + (g_tw.to(params[16].dtype),
                                                                              g_txw.to(params[17].dtype))
 
 

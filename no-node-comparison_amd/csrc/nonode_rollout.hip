@@ -69,6 +69,34 @@ __global__ __launch_bounds__(256) void featurize_kernel(FeatArgs a) {
   }
 }
 
+// Reverse of featurize_kernel for the outputs the reference keeps on the autograd tape (x_out, v_out,
+// loc_mean; nodes and edge_attr are detached, main_simulation_simple_no.py:321-338). One block per
+// graph: the per-graph mean's gradient (1/N) sum_m g_lm[b][m] added in node order by one thread per
+// coordinate (deterministic), then every frame of the graph written (zero but in the selected frame).
+__global__ __launch_bounds__(256) void featurize_bwd_kernel(int B, int N, int F, const int* t_in, const float* g_x,
+                                                            const float* g_v, const float* g_lm, float* g_loc,
+                                                            float* g_vel) {
+  __shared__ float sm[3];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int fsel = F - 1;
+  if (t_in) fsel = ((t_in[b] - 1) % F + F) % F;
+  const size_t BN = (size_t)B * N, r0 = (size_t)b * N;
+  if (tid < 3) {
+    float m = 0.f;
+    if (g_lm)
+      for (int i = 0; i < N; ++i) m += g_lm[(r0 + i) * 3 + tid];
+    sm[tid] = m / (float)N;
+  }
+  __syncthreads();
+  for (int k = tid; k < F * N * 3; k += 256) {
+    const int f = k / (N * 3), e = k - f * (N * 3);
+    const size_t src = r0 * 3 + e, dst = ((size_t)f * BN + r0) * 3 + e;
+    const bool sel = f == fsel;
+    if (g_loc) g_loc[dst] = sel ? (g_x ? g_x[src] : 0.f) + sm[e % 3] : 0.f;
+    if (g_vel) g_vel[dst] = sel && g_v ? g_v[src] : 0.f;
+  }
+}
+
 // Energy of F frames x B graphs: one wave per (frame, graph), lanes over receivers i, f64 sums.
 //   kind 0 (charged): 0.5 sum |v|^2 + 0.5 sum_{i != j} q_i q_j / |x_i - x_j|   (0 where the distance is 0)
 //   kind 1 (gravity): 0.5 sum m |v|^2 - sum_{i < j} m_i m_j / |x_i - x_j|      (G = 1)
@@ -207,6 +235,16 @@ int nonode_prepare_inputs(int B, int N, int F, const float* loc, const float* ve
     return fail(NONODE_EINVAL, "prepare_inputs: null pointer");
   FeatArgs a{B, N, F, n_eo, loc, vel, t_in, charges, edge_attr_o, x_out, v_out, nodes, edge_attr, loc_mean};
   return launch_featurize(a, (hipStream_t)stream);
+}
+
+int nonode_prepare_inputs_bwd(int B, int N, int F, const int* t_in, const float* g_x, const float* g_v,
+                              const float* g_lm, float* g_loc, float* g_vel, void* stream) {
+  if (B <= 0 || N < 2 || F <= 0 || (long long)F * N * 3 >= (1ll << 31))
+    return fail(NONODE_EINVAL, "prepare_inputs_bwd: B=%d N=%d F=%d", B, N, F);
+  if (!g_loc && !g_vel) return NONODE_OK;
+  hipLaunchKernelGGL(featurize_bwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, B, N, F, t_in, g_x, g_v, g_lm,
+                     g_loc, g_vel);
+  return check_launch("featurize_bwd_kernel");
 }
 
 int nonode_energy(int kind, int F, int B, int N, const float* loc, const float* vel, const float* weights,

@@ -1596,6 +1596,142 @@ __global__ __launch_bounds__(TX_THREADS) void tconvx_bwd_kernel(int BN, int T, i
   }
 }
 
+// ---- input gradients (nonode_egno_backward_inputs) -------------------------------------------------
+// Frame t of the forward read input slot fi[t] (x.repeat / v.repeat, egno.py:89-96; the multi-input
+// model's repeat_elements_to_exact_shape): every input gradient is a sum over the frames of a slot.
+// One thread (h: one wave) owns an output element and adds its frames in frame order: deterministic.
+struct FrameSlots { int n_inputs; int fi[TMAX]; };
+
+// TB: compile-time frame bound (10 for T <= 10, else TMAX), as in tconvx_bwd_kernel: every frame's load is
+// issued up front, unconditionally with the frame index clamped to T - 1 (a runtime frame loop paid one
+// memory latency per frame: 7.5 us for input_xv_grad_kernel and 10 us for input_lm_grad_kernel at C4)
+
+// g_x_in[i][e] = sum_{t: fi[t] = i} gx0[t][e] over the BN * 3 elements e of a frame, and g_v_in from
+// gv0 likewise (either output may be null)
+template <int TB>
+__global__ __launch_bounds__(256) void input_xv_grad_kernel(int BN3, int T, FrameSlots fs, const float* gx0,
+                                                            const float* gv0, float* g_x_in, float* g_v_in) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= BN3) return;
+  float ax[TB], av[TB];
+#pragma unroll
+  for (int t = 0; t < TB; ++t) {
+    const size_t o = (size_t)(t < T ? t : T - 1) * BN3 + e;
+    ax[t] = g_x_in ? gx0[o] : 0.f;
+    av[t] = g_v_in ? gv0[o] : 0.f;
+  }
+  for (int i = 0; i < fs.n_inputs; ++i) {
+    float sx = 0.f, sv = 0.f;
+#pragma unroll
+    for (int t = 0; t < TB; ++t) {
+      const bool on = t < T && fs.fi[t] == i;
+      sx += on ? ax[t] : 0.f;
+      sv += on ? av[t] : 0.f;
+    }
+    if (g_x_in) g_x_in[(size_t)i * BN3 + e] = sx;
+    if (g_v_in) g_v_in[(size_t)i * BN3 + e] = sv;
+  }
+}
+
+// g_h_in[i][c][k] = sum_o (sum_{t: fi[t] = i} gh0[t][c][o]) W_emb[o][k], k < din (the embedding Linear,
+// egno.py:63-76, is linear: the frames are added first, one product per node and slot). One wave per
+// node c, lane = o: a single pass over gh0; the 64 x din weight columns staged in LDS.
+template <int TB>
+__global__ __launch_bounds__(256) void input_h_grad_kernel(int BN, int T, int din, int ld, FrameSlots fs,
+                                                           const float* __restrict__ gh0,
+                                                           const float* __restrict__ emb_w, float* g_h_in) {
+  __shared__ float sW[64 * 8];
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int cc = c < BN ? c : BN - 1;   // (loads before the barrier: a valid row for the waves past the end)
+  float a[TB];
+#pragma unroll
+  for (int t = 0; t < TB; ++t) a[t] = gh0[((size_t)(t < T ? t : T - 1) * BN + cc) * 64 + lane];
+  for (int i = threadIdx.x; i < 64 * din; i += 256) sW[i] = emb_w[(size_t)(i / din) * ld + i % din];
+  __syncthreads();
+  if (c >= BN) return;   // (wave-uniform, after the only barrier)
+  for (int i = 0; i < fs.n_inputs; ++i) {
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < TB; ++t) s += (t < T && fs.fi[t] == i) ? a[t] : 0.f;
+    for (int k = 0; k < din; ++k) {
+      float p = s * sW[lane * din + k];
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) p += __shfl_xor(p, o);
+      if (lane == 0) g_h_in[((size_t)i * BN + c) * din + k] = p;
+    }
+  }
+}
+
+// g_loc_mean of ONE layer's TimeConv_x (egno.py:103-107: X0 = x - lm, x = (X + spectral(X))_0 + lm): the
+// identity parts cancel, leaving minus the adjoint of the spectral term on the x channel,
+//   g_lm[i][c][d] (+)= - sum_{t: fi[t] = i} sum_m (gxr_m cos(2 pi m t / T) - gxi_m sin(2 pi m t / T)),
+// with gxr, gxi as in tconvx_bwd_kernel (input channel 0) from the output gradients gxo, gvo. Taken from
+// that term directly: the difference gxo - g_xin of the two x gradients would cancel leading digits.
+// One thread per (column c, coordinate d); accumulate = 0 for the first layer of the reverse pass.
+template <int TB>
+__global__ __launch_bounds__(TX_THREADS) void input_lm_grad_kernel(int BN, int T, int M, int Mfull, FrameSlots fs,
+                                                                   const float* gxo, const float* gvo,
+                                                                   const float* w, float* g_lm, int accumulate) {
+  __shared__ float sCs[MMAX_T * TMAX], sSn[MMAX_T * TMAX];
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = idx < BN * 3;
+  const size_t ii = valid ? idx : 0;
+  float GO[2][TB];   // requested before the twiddle table is built
+#pragma unroll
+  for (int t = 0; t < TB; ++t) {
+    const size_t o = (size_t)(t < T ? t : T - 1) * BN * 3 + ii;
+    GO[0][t] = gxo[o];
+    GO[1][t] = gvo[o];
+  }
+  for (int i = threadIdx.x; i < M * T; i += blockDim.x) {
+    const int m = i / T, t = i - m * T;
+    const double ang = 2.0 * (double)m * (double)t / (double)T;
+    sCs[m * TMAX + t] = (float)cospi(ang);
+    sSn[m * TMAX + t] = (float)sinpi(ang);
+  }
+  __syncthreads();
+  if (!valid) return;
+  float spec[TB];   // the spectral adjoint on the x channel, per frame
+#pragma unroll
+  for (int t = 0; t < TB; ++t) spec[t] = 0.f;
+#pragma unroll
+  for (int m = 0; m < MMAX_T; ++m) {
+    if (m >= M) break;
+    const float cm = ((m == 0 || 2 * m == T) ? 1.f : 2.f) / (float)T;
+    float gYr[2] = {0.f, 0.f}, gYi[2] = {0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < TB; ++t) {
+      if (t >= T) break;
+      const float cs = sCs[m * TMAX + t], sn = sSn[m * TMAX + t];
+#pragma unroll
+      for (int o = 0; o < 2; ++o) {
+        gYr[o] = fmaf(cm * cs, GO[o][t], gYr[o]);
+        gYi[o] = fmaf(-cm * sn, GO[o][t], gYi[o]);
+      }
+    }
+    float gxr = 0.f, gxi = 0.f;
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      const float wr = w[(o * Mfull + m) * 2 + 0], wi = w[(o * Mfull + m) * 2 + 1];   // input channel 0
+      gxr += gYr[o] * wr + gYi[o] * wi;
+      gxi += -gYr[o] * wi + gYi[o] * wr;
+    }
+#pragma unroll
+    for (int t = 0; t < TB; ++t) {
+      if (t >= T) break;
+      spec[t] += gxr * sCs[m * TMAX + t] - gxi * sSn[m * TMAX + t];
+    }
+  }
+  for (int i = 0; i < fs.n_inputs; ++i) {
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < TB; ++t) s += (t < T && fs.fi[t] == i) ? spec[t] : 0.f;
+    float* p = g_lm + (size_t)i * BN * 3 + idx;
+    *p = accumulate ? *p - s : -s;
+  }
+}
+
 // ---- embedding Linear gradient (egno.py:63-76 reversed) ------------------------------------------
 // dW[o][k] = sum over the rows r = t BN + c of gh0[r][o] in[r][k] and db[o] = sum_r gh0[r][o], where the
 // embedding's input row is in[r] = [h_in[frames ? r : c], trig[(c % Bt) T + t]]: the raw time embedding
@@ -2203,11 +2339,30 @@ int egno_backward_impl(int frames, int emb_cols, int B, int N, int T, int n_laye
                          const float* const* bblobs, const float* const* tconv_w, const float* const* tconvx_w,
                          const void* state, const float* g_x, const float* g_v, const float* g_h,
                          const nonode_layer_grads* layer_grads, float* const* g_tconv, float* const* g_tconvx,
-                         float* g_emb_w, float* g_emb_b, void* workspace, size_t workspace_bytes, void* stream) {
+                         float* g_emb_w, float* g_emb_b, void* workspace, size_t workspace_bytes, void* stream,
+                         const nonode_input_grads* ig = nullptr) {
   if (B <= 0 || N < 2 || T <= 0 || T > TMAX || n_layers < 1 || modes < 1 || modes > MMAX_T || Bt <= 0 ||
       n_edge_feat < 0 || n_edge_feat > 4)
     return fail(NONODE_EUNSUPPORTED, "egno_backward: B=%d N=%d T=%d", B, N, T);
   const bool tc = tconv_w != nullptr;   // false: use_time_conv=False (every TimeConv array null)
+  // input gradients (nonode_egno_backward_inputs): none asked for = the launches of the plain entries
+  if (ig && !ig->g_x_in && !ig->g_v_in && !ig->g_h_in && !ig->g_loc_mean) ig = nullptr;
+  FrameSlots fs{};
+  if (ig) {
+    fs.n_inputs = ig->n_inputs;
+    if (ig->n_inputs < 1 || ig->n_inputs > T || (!frames && ig->n_inputs != 1) ||
+        (ig->n_inputs > 1 && !ig->frame_input) || in_node < 0 || in_node > 8)
+      return fail(NONODE_EINVAL, "egno_backward_inputs: n_inputs=%d (T=%d, frames=%d) in_node=%d", ig->n_inputs, T,
+                  frames, in_node);
+    for (int t = 0; t < T; ++t) {
+      fs.fi[t] = ig->frame_input ? ig->frame_input[t] : 0;
+      if (fs.fi[t] < 0 || fs.fi[t] >= ig->n_inputs)
+        return fail(NONODE_EINVAL, "egno_backward_inputs: frame_input[%d]=%d of %d inputs", t, fs.fi[t], ig->n_inputs);
+    }
+    if (ig->g_h_in && in_node > 0 && !ig->emb_w) return fail(NONODE_EINVAL, "egno_backward_inputs: g_h_in needs emb_w");
+    if (ig->g_loc_mean && !tc)
+      return fail(NONODE_EINVAL, "egno_backward_inputs: loc_mean has no gradient without time convolutions");
+  }
   if ((tc && (!loc_mean || !tconvx_w || !g_tconv || !g_tconvx)) ||
       (!tc && (tconvx_w || g_tconv || g_tconvx)) || !bblobs || !state || !g_x || !layer_grads ||
       !g_emb_w || !g_emb_b || !workspace || (n_edge_feat > 0 && !edge_fea))
@@ -2260,6 +2415,12 @@ int egno_backward_impl(int frames, int emb_cols, int B, int N, int T, int n_laye
     tr.gh = w.ghe; tr.gx = w.gxe; tr.gv = w.gve;
     tr.g_hin = w.gh[nxt]; tr.g_xin = w.gx[nxt]; tr.g_vin = w.gv[nxt]; tr.g_tw = g_tconv[l]; tr.g_txw = g_tconvx[l];
     if (int rc = tconv_reverse(tr, w, s, &dr)) return rc;
+    if (ig && ig->g_loc_mean) {   // this layer's x - loc_mean ... + loc_mean (layers in stream order)
+      hipLaunchKernelGGL(T <= 10 ? input_lm_grad_kernel<10> : input_lm_grad_kernel<TMAX>,
+                         dim3((BN * 3 + TX_THREADS - 1) / TX_THREADS), dim3(TX_THREADS), 0, s, BN, T, M, modes, fs, w.gxe,
+                         w.gve, tconvx_w[l], ig->g_loc_mean, l != L - 1);
+      if (int rc = check_launch("input_lm_grad_kernel")) return rc;
+    }
     cur = nxt;
     gx = w.gx[cur]; gv = w.gv[cur]; gh = w.gh[cur];
   }
@@ -2287,11 +2448,35 @@ int egno_backward_impl(int frames, int emb_cols, int B, int N, int T, int n_laye
                              nullptr, 0, 1.f, 1 << 30, 0, (long long)64 * (emb_ld - 64 + 1)};
     if (int rc = launch_reduce_batch(jobs, nj, s)) return rc;
   }
+  // ---- input gradients: gx, gv, gh now hold the gradients of the first layer's inputs [T][BN][.] ----
+  if (ig && (ig->g_x_in || ig->g_v_in)) {
+    hipLaunchKernelGGL(T <= 10 ? input_xv_grad_kernel<10> : input_xv_grad_kernel<TMAX>, dim3((BN * 3 + 255) / 256),
+                       dim3(256), 0, s, BN * 3, T, fs, gx, gv, ig->g_x_in, ig->g_v_in);
+    if (int rc = check_launch("input_xv_grad_kernel")) return rc;
+  }
+  if (ig && ig->g_h_in && in_node > 0) {
+    hipLaunchKernelGGL(T <= 10 ? input_h_grad_kernel<10> : input_h_grad_kernel<TMAX>, dim3((BN + 3) / 4), dim3(256), 0,
+                       s, BN, T, in_node, in_node + emb_cols, fs, gh, ig->emb_w, ig->g_h_in);
+    if (int rc = check_launch("input_h_grad_kernel")) return rc;
+  }
   return NONODE_OK;
 }
 }  // namespace
 
 extern "C" {
+
+int nonode_egno_backward_inputs(int frames, int B, int N, int T, int n_layers, int in_node, int n_edge_feat,
+                                int time_emb_dim, int with_t_in, int modes, int Bt, const float* loc_mean,
+                                const float* edge_fea, const float* const* bblobs, const float* const* tconv_w,
+                                const float* const* tconvx_w, const void* state, const float* g_x, const float* g_v,
+                                const float* g_h, const nonode_layer_grads* layer_grads, float* const* g_tconv,
+                                float* const* g_tconvx, float* g_emb_w, float* g_emb_b, void* workspace,
+                                size_t workspace_bytes, void* stream, const nonode_input_grads* inputs) {
+  return egno_backward_impl(frames ? 1 : 0, ((frames && with_t_in) ? 2 : 1) * time_emb_dim, B, N, T, n_layers, in_node,
+                            n_edge_feat, time_emb_dim, modes, Bt, loc_mean, edge_fea, bblobs, tconv_w, tconvx_w, state,
+                            g_x, g_v, g_h, layer_grads, g_tconv, g_tconvx, g_emb_w, g_emb_b, workspace, workspace_bytes,
+                            stream, inputs);
+}
 
 int nonode_egno_backward(int B, int N, int T, int n_layers, int in_node, int n_edge_feat, int time_emb_dim,
                          int modes, int Bt, const float* loc_mean, const float* edge_fea,

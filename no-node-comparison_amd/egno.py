@@ -264,7 +264,13 @@ class EGNO(nn.Module):
         if v is None or (loc_mean is None and self.use_time_conv):
             raise ValueError("EGNO.forward needs v and loc_mean (the time convolution stacks "
                              "x - loc_mean with v, egno.py:103-105)")
-        if self.flat and self._trains() and self.num_inputs > 1:
+        if torch.is_grad_enabled() and edge_fea is not None and edge_fea.requires_grad:
+            raise NotImplementedError(
+                "EGNO.forward has no gradient for edge_fea: the reference's training and rollout loops detach "
+                "the edge features (main_simulation_simple_no.py:327,338) and the per-edge input gradient is "
+                "not built; pass edge_fea.detach()")
+        tapes = self._tapes(x, h, v, loc_mean)
+        if self.flat and tapes and self.num_inputs > 1:
             raise NotImplementedError("EGNO(flat=True) training runs the single-input model (num_inputs=1)")
         if self.num_inputs > 1:
             return self._forward_multi(x, h, edge_index, edge_fea, v, loc_mean, timesteps_in, timesteps_out)
@@ -281,7 +287,7 @@ class EGNO(nn.Module):
         B, N = check_full_graph(edge_index, BN)
         if edge_fea.shape != (B * N * (N - 1), self.in_edge_nf):
             raise ValueError(f"edge_fea must be [{B * N * (N - 1)}, {self.in_edge_nf}], got {tuple(edge_fea.shape)}")
-        if self._trains():
+        if tapes:
             if self.flat:
                 from .autograd import egno_flat_train
                 return finish(egno_flat_train(self, x, h, edge_fea, v, loc_mean, timesteps_out, B, N))
@@ -293,6 +299,13 @@ class EGNO(nn.Module):
         """Training forward: train mode, gradients enabled and a parameter that requires grad."""
         return self.training and torch.is_grad_enabled() and any(
             p.requires_grad for p in _lib.param_list(self, "all", lambda: list(self.parameters())))
+
+    def _tapes(self, x, h, v, loc_mean):
+        """The forward goes on the autograd tape: a training forward (_trains), or, in any module mode,
+        gradients enabled and an input among x, h, v, loc_mean that requires grad (the reference's
+        forward is plain torch and differentiates with respect to them)."""
+        return self._trains() or (torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in (x, h, v, loc_mean)))
 
     def frame_inputs(self, T):
         """Input index of each of the T frames: repeat_elements_to_exact_shape (EGNO/utils.py:115-131)
@@ -329,9 +342,12 @@ class EGNO(nn.Module):
             xf, hf, vf, lmf, eff = (per_frame(t) for t in (x, h, v, loc_mean, edge_fea))
             t_in = f32(timesteps_in)[:, fidx].contiguous()
             t_out = f32(timesteps_out).contiguous()
-        if self._trains():
+        if self._tapes(x, h, v, loc_mean):
+            # the tape's inputs are the caller's per-slot tensors (their gradients: the frames of a slot
+            # summed by the kernels); the kernels read the per-frame copies
             from .autograd import egno_forward_train
-            return finish(egno_forward_train(self, xf, hf, eff, vf, lmf, t_out, B, N, t_in=t_in))
+            return finish(egno_forward_train(self, x, h, eff, v, loc_mean, t_out, B, N, t_in=t_in,
+                                             slots=(self.frame_inputs(T), (xf, hf, vf, lmf))))
         L = _lib.lib()
         with torch.no_grad():
             return finish(self._launch_forward(L.nonode_egno_forward_flat if self.flat else L.nonode_egno_forward_frames,

@@ -26,14 +26,26 @@ def get_edges(batch_size, n_nodes, device="cpu"):
     return [r, c]
 
 
-@torch.no_grad()
 def prepare_inputs(loc, vel, edge_attr_o, edges, n_nodes, num_inputs=1, charges=None, t_in=None):
     """main_simulation_simple_no.py:311-339 (nonode_prepare_inputs; num_inputs > 1 per input slot).
 
     loc, vel: [B, N, 3] (one frame) or [F, B, N, 3] with ``t_in`` [B] choosing frame t_in-1 per
     sample (rollout_fn's loc_all[timesteps_in.T - 1]). edges must be the dataset's fully connected
     list (only its size is used: the kernel indexes pairs implicitly). Returns
-    (loc [BN,3], vel [BN,3], edge_attr [E, n_eo+1], nodes [BN, 1(+1)], loc_mean [BN,3])."""
+    (loc [BN,3], vel [BN,3], edge_attr [E, n_eo+1], nodes [BN, 1(+1)], loc_mean [BN,3]).
+
+    num_inputs == 1 with gradients enabled and a loc or vel that requires grad: the returned loc, vel
+    and loc_mean are on the autograd tape (backward: nonode_prepare_inputs_bwd), as in the reference;
+    nodes and edge_attr are detached, as the reference detaches them (:333, :338)."""
+    if num_inputs == 1 and torch.is_grad_enabled() and (loc.requires_grad or vel.requires_grad):
+        x, v, lm, ea, nodes = _PrepareInputs.apply(loc, vel, edge_attr_o, edges, n_nodes, charges, t_in)
+        return x, v, ea, nodes, lm
+    with torch.no_grad():
+        return _prepare_inputs(loc, vel, edge_attr_o, edges, n_nodes, num_inputs, charges, t_in)
+
+
+def _prepare_inputs(loc, vel, edge_attr_o, edges, n_nodes, num_inputs=1, charges=None, t_in=None):
+    """prepare_inputs off the tape (callers hold torch.no_grad())."""
     if num_inputs > 1:
         return _prepare_inputs_multi(loc, vel, edge_attr_o, edges, n_nodes, num_inputs, charges)
     _lib.require_device(loc, vel, edge_attr_o, charges)
@@ -64,6 +76,37 @@ def prepare_inputs(loc, vel, edge_attr_o, edges, n_nodes, num_inputs=1, charges=
     return x, v, ea, nodes, lm
 
 
+class _PrepareInputs(torch.autograd.Function):
+    """prepare_inputs (num_inputs == 1) on the autograd tape for loc and vel: forward the featurisation
+    kernel, backward nonode_prepare_inputs_bwd (the selected frame gets g_x + the per-graph mean of
+    g_loc_mean and g_v, every other frame zero)."""
+
+    @staticmethod
+    def forward(ctx, loc, vel, edge_attr_o, edges, n_nodes, charges, t_in):
+        x, v, ea, nodes, lm = _prepare_inputs(loc, vel, edge_attr_o, edges, n_nodes, 1, charges, t_in)
+        ctx.shape, ctx.dtypes = tuple(loc.shape), (loc.dtype, vel.dtype)
+        ctx.ti = t_in.reshape(-1).to(torch.int32).contiguous() if t_in is not None else None
+        ctx.mark_non_differentiable(ea, nodes)
+        ctx.set_materialize_grads(False)
+        return x, v, lm, ea, nodes
+
+    @staticmethod
+    def backward(ctx, gx, gv, glm, _gea, _gnodes):
+        shape = ctx.shape if len(ctx.shape) == 4 else (1,) + ctx.shape
+        F, B, N = shape[0], shape[1], shape[2]
+        ref = next(g for g in (gx, gv, glm) if g is not None)
+        dev = ref.device
+        gx, gv, glm = _f32(gx), _f32(gv), _f32(glm)
+        g_loc = torch.empty(shape, device=dev) if ctx.needs_input_grad[0] else None
+        g_vel = torch.empty(shape, device=dev) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.lib().nonode_prepare_inputs_bwd(B, N, F, _lib.ptr(ctx.ti), _lib.ptr(gx), _lib.ptr(gv),
+                                                        _lib.ptr(glm), _lib.ptr(g_loc), _lib.ptr(g_vel),
+                                                        _lib.stream_of(ref)))
+        g_loc = g_loc.reshape(ctx.shape).to(ctx.dtypes[0]) if g_loc is not None else None
+        g_vel = g_vel.reshape(ctx.shape).to(ctx.dtypes[1]) if g_vel is not None else None
+        return g_loc, g_vel, None, None, None, None, None
+
+
 def _prepare_inputs_multi(loc, vel, edge_attr_o, edges, n_nodes, num_inputs, charges):
     """main_simulation_simple_no.py:313-327 (num_inputs = I > 1), literally: loc, vel are transposed
     on their first two axes and reshaped to I slots of B*N rows ([B, I, N, 3] from the loader gives
@@ -73,7 +116,7 @@ def _prepare_inputs_multi(loc, vel, edge_attr_o, edges, n_nodes, num_inputs, cha
     I = num_inputs
     lt = loc.transpose(0, 1).contiguous().reshape(I, -1, n_nodes, 3)
     vt = vel.transpose(0, 1).contiguous().reshape(I, -1, n_nodes, 3)
-    outs = [prepare_inputs(lt[i], vt[i], edge_attr_o, edges, n_nodes, 1, charges) for i in range(I)]
+    outs = [_prepare_inputs(lt[i], vt[i], edge_attr_o, edges, n_nodes, 1, charges) for i in range(I)]
     x, v, ea, nodes, lm = (torch.stack([o[k] for o in outs]) for k in range(5))
     return x, v, ea, nodes, lm
 
@@ -188,6 +231,39 @@ def egno_rollout(model, nodes, loc, edges, vel, edge_attr_o, edge_attr, loc_mean
         return preds, None, None
     en_all = en_all.unsqueeze(-1)
     return preds, en_all[T - 1::T], en_all
+
+
+def egno_rollout_train(model, nodes, loc, edges, vel, edge_attr_o, edge_attr, loc_mean, n_nodes, traj_len,
+                       batch_size, charges=None, num_steps=10, timesteps_in=None, timesteps_out=None):
+    """The loop of rollout_fn (main_simulation_simple_no.py:357-371), num_inputs == 1, on the autograd
+    tape: per segment model(...), then frame timesteps_in - 1 of each sample (None: the last) through the
+    differentiable prepare_inputs, so a loss on the returned loc_preds [traj_len*T, BN, 3] backpropagates
+    through every segment to the parameters and to the initial loc, vel, loc_mean (unrolled rollout
+    training). nodes and edge_attr are re-featurised detached, as the reference does; no energies.
+    Several inputs (num_inputs > 1) are not unrolled: ValueError."""
+    from .egno import EGNO
+    if not isinstance(model, EGNO):
+        raise TypeError("egno_rollout_train drives no_node_comparison_amd.EGNO")
+    if model.num_inputs > 1 or (timesteps_in is not None and timesteps_in.dim() == 2 and timesteps_in.shape[1] > 1):
+        raise ValueError("egno_rollout_train unrolls the single-input model (num_inputs == 1)")
+    T = model.num_timesteps
+    if num_steps != T:
+        raise ValueError("rollout_fn reshapes each segment into num_steps == model.num_timesteps frames")
+    B, N = batch_size, n_nodes
+    if timesteps_out is None:
+        timesteps_out = torch.arange(T * traj_len, device=loc.device).unsqueeze(0)
+    if timesteps_out.shape[1] != T * traj_len:
+        raise ValueError(f"timesteps_out must have {T * traj_len} columns")
+    ti = timesteps_in.reshape(-1) if timesteps_in is not None else None
+    preds = []
+    for i in range(traj_len):
+        t_out = timesteps_out[:, i * T:(i + 1) * T] - i * T
+        x, v, _ = model(loc, nodes, edges, edge_attr, v=vel, loc_mean=loc_mean, timesteps_out=t_out)
+        preds.append(x.reshape(T, B * N, 3))
+        if i + 1 < traj_len:
+            loc, vel, edge_attr, nodes, loc_mean = prepare_inputs(x.reshape(T, B, N, 3), v.reshape(T, B, N, 3),
+                                                                  edge_attr_o, edges, N, 1, charges, t_in=ti)
+    return torch.cat(preds)
 
 
 @torch.no_grad()

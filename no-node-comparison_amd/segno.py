@@ -136,6 +136,12 @@ class SEGNO(nn.Module):
         return self.training and torch.is_grad_enabled() and any(
             p.requires_grad for p in _lib.param_list(self, "all", lambda: list(self.parameters())))
 
+    def _tapes(self, *inputs):
+        """The single-input forward goes on the autograd tape: training (_training), or, in any module
+        mode, gradients enabled and an input (his / h, x, v) that requires grad."""
+        return self._training() or (torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in inputs))
+
     def _packed(self):
         params = _lib.param_list(self, "gcl", lambda: list(self.module.parameters()))
         key = tuple((p.data_ptr(), p._version) for p in params)
@@ -163,9 +169,9 @@ class SEGNO(nn.Module):
         if self.bug_compat:
             # the live reference forward returns its inputs (and the embedded h)
             return x, self._embed(his), v
-        if self._training():
+        if self._tapes(his, x, v):
             if his.shape[-1] > 40:   # (nonode_embedding_* take up to 40 input features)
-                return self._step(self._embed(his), x, edges, v, edge_attr, int(T))
+                return self._step(self._embed(his), x, edges, v, edge_attr, int(T), tape=True)
             # the embedding and the T substeps as one autograd node (autograd.SEGNOTrain)
             B, N = self._check_inputs(x, edges, v, edge_attr)
             _lib.require_device(his, self.embedding.weight)
@@ -211,12 +217,12 @@ class SEGNO(nn.Module):
         """model.py:95-102: T substeps of the shared layer from an already-embedded h."""
         self.module.n_layers = T
         self.n_layers = T
-        return self._step(h, x, edges, v, edge_attr, int(T))
+        return self._step(h, x, edges, v, edge_attr, int(T), tape=self._tapes(h, x, v))
 
-    def _step(self, h, x, edges, v, edge_attr, T):
-        """forward_step from an embedded h: on the autograd tape in training, else the fused
-        inference launch."""
-        if not self._training():
+    def _step(self, h, x, edges, v, edge_attr, T, tape=None):
+        """forward_step from an embedded h: on the autograd tape in training (tape: the caller's own
+        decision, the single-input forms' _tapes), else the fused inference launch."""
+        if not (self._training() if tape is None else tape):
             return self._run(None, h, x, edges, v, edge_attr, T)
         _lib.require_device(h)
         B, N = self._check_inputs(x, edges, v, edge_attr)
