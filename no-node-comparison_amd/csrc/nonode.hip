@@ -245,6 +245,10 @@ struct LayerArgs {
   // k % 8 (its XCD) owns the same 1/8 of the columns as the TimeConv tiles on that XCD
   int use_perm;
   unsigned short chunk_of[256];
+  // EGNO, four waves, whole-graph chunks: the unit split (unit_split) of the launch's chunk shapes,
+  // computed once on the host by the function the kernel would run: the full chunk of cg graphs and
+  // the short last one. hc_n shapes; shape i has hc_ctc[i] tiles, hc_vl[i] receivers in the last tile.
+  int hc_n, hc_ctc[2], hc_vl[2], hc_cut[2][5];
 };
 
 // LDS of one chunk: ct receiver tiles (P, two message-sum slots, two force-sum slots) and s_rows senders
@@ -285,6 +289,8 @@ template <int VARIANT, int KF, int NW, bool OPT, bool SAVE = false>
 __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)[NW + 1]) {
   constexpr bool PAIR = NW == 4;
   constexpr bool TRIPLE = PAIR && VARIANT == EGNO;   // three-unit iterations before the pairs
+  constexpr bool FSPLIT = TRIPLE && NONODE_FSPLIT != 0;   // first SiLU fused into the fp16x3 split
+  constexpr bool HOSTCUT = TRIPLE && NONODE_HOSTCUT != 0;   // the chunk shapes' unit splits come with the launch
   [[maybe_unused]] constexpr bool stamp_here = VARIANT == EGNO && NW == 4 && !OPT;   // (NONODE_STAMP builds)
   constexpr bool rnorm = OPT && VARIANT == EGNO;    // basic.py:140-141
   constexpr bool ctanh = OPT && VARIANT == SEGNO;   // gcl.py:57-59
@@ -537,7 +543,17 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
         cut_ctc = ctc;
         cut_vl = Vl;
         if constexpr (PAIR) {   // four waves: any tile spans at most four; ranges balanced by modelled cost
-          unit_split<NW>(ctc, Nm1, Ul, Pk == 1 ? Nm1 : Kp, cut);
+          bool have = false;
+          if constexpr (HOSTCUT) {   // the launch brought this shape's split (every shape of whole-graph chunks)
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+              if (!have && i < p.hc_n && p.hc_ctc[i] == ctc && p.hc_vl[i] == Vl) {
+#pragma unroll
+                for (int j = 0; j <= NW; ++j) cut[j] = p.hc_cut[i][j];
+                have = true;
+              }
+          }
+          if (!have) unit_split<NW, TRIPLE && NONODE_TRICOST != 0>(ctc, Nm1, Ul, Pk == 1 ? Nm1 : Kp, cut);
         } else {                // eight waves: every wave's range holds at least a third of a tile
           const int NWB = min(NW, 3 * ctc);
           for (int i = 0; i <= NW; ++i) cut[i] = i < NWB ? (i * U) / NWB : U;
@@ -719,12 +735,16 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
           fetch_ef(min(k + 1, kp_hi) + kof, e1);
           // EGNO: three units per iteration first, a third independent chain for the stalls at the
           // stage boundaries (C2 layer -1.5 us; SEGNO's C3 launch measured
-          // +1 us with it, so SEGNO keeps pairs only); then pairs, then single units
-          if (TRIPLE && k + 2 <= kp_hi) {
+          // +1 us with it, so SEGNO keeps pairs only); then pairs, then single units. The counts are
+          // seg_walk's: its triples here, and the pair loop below takes what is left two by two (one
+          // pair, or the two pairs of a 3 t + 1 run), so only a run of one unit reaches the single loop
+          const int k3_end = k + 3 * seg_walk<TRIPLE>(kp_hi - k + 1).tri;
+          STAMP(5);   // (segment prologue; 4: a triple iteration, 0-3: a pair's stages, 14: a single unit)
+          if (TRIPLE && k < k3_end) {
             float e2[KF];
             fetch_ef(min(k + 2, kp_hi) + kof, e2);
 #pragma unroll 1
-            for (; k + 2 <= kp_hi; k += 3) {
+            for (; k < k3_end; k += 3) {
               float n0[KF], n1[KF], n2[KF];
               fetch_ef(min(k + 3, kp_hi) + kof, n0);
               fetch_ef(min(k + 4, kp_hi) + kof, n1);
@@ -737,16 +757,24 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
               head2(k + kof, e0, a0, r00, r01, r02, okA);
               head2(k + 1 + kof, e1, a1, r10, r11, r12, okB);
               head2(k + 2 + kof, e2, a2, r20, r21, r22, okC);
-              silu_ecl(a0);
-              silu_ecl(a1);
-              silu_ecl(a2);
+              if constexpr (!FSPLIT) {
+                silu_ecl(a0);
+                silu_ecl(a1);
+                silu_ecl(a2);
+              }
 #pragma unroll
               for (int mt = 0; mt < 4; ++mt) { m0[mt] = rB2[mt]; m1[mt] = rB2[mt]; m2[mt] = rB2[mt]; }
               {
                 h8 ah0[2], al0[2], ah1[2], al1[2], ah2[2], al2[2];
-                h16_split(a0, ah0, al0);
-                h16_split(a1, ah1, al1);
-                h16_split(a2, ah2, al2);
+                if constexpr (FSPLIT) {   // SiLU and split in one: its f32 result has no other consumer
+                  silu_split(a0, ah0, al0);
+                  silu_split(a1, ah1, al1);
+                  silu_split(a2, ah2, al2);
+                } else {
+                  h16_split(a0, ah0, al0);
+                  h16_split(a1, ah1, al1);
+                  h16_split(a2, ah2, al2);
+                }
                 mfma_h16r3(m0, m1, m2, rw2, ah0, al0, ah1, al1, ah2, al2, us_w2);
               }
               silu_ecl(m0);
@@ -786,6 +814,7 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
               fs0 += (f00 + f10) + f20; fs1 += (f01 + f11) + f21; fs2 += (f02 + f12) + f22;
 #pragma unroll
               for (int kf = 0; kf < KF; ++kf) { e0[kf] = n0[kf]; e1[kf] = n1[kf]; e2[kf] = n2[kf]; }
+              STAMP(4);
             }
           }
 #pragma unroll 1
@@ -802,14 +831,21 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
             head2(k + kof, e0, a0, r00, r01, r02, okA);
             head2(k + 1 + kof, e1, a1, r10, r11, r12, okB);
             STAMP(0);
-            silu_ecl(a0);
-            silu_ecl(a1);
+            if constexpr (!FSPLIT) {
+              silu_ecl(a0);
+              silu_ecl(a1);
+            }
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) { m0[mt] = rB2[mt]; m1[mt] = rB2[mt]; }
             {
               h8 ah0[2], al0[2], ah1[2], al1[2];
-              h16_split(a0, ah0, al0);
-              h16_split(a1, ah1, al1);
+              if constexpr (FSPLIT) {
+                silu_split(a0, ah0, al0);
+                silu_split(a1, ah1, al1);
+              } else {
+                h16_split(a0, ah0, al0);
+                h16_split(a1, ah1, al1);
+              }
               mfma_h16r2(m0, m1, rw2, ah0, al0, ah1, al1, us_w2);
             }
             STAMP(1);
@@ -984,7 +1020,6 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
           head(lane_k(k), e0, a, r0, r1, r2);
 #pragma unroll
           for (int kf = 0; kf < KF; ++kf) e0[kf] = en[kf];
-          STAMP(0);
           silu_ecl(a);
           if (PAIR) {
 #pragma unroll
@@ -999,7 +1034,6 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
             h16_split(a, ah, al);
             mfma_h16(m, w2l, ah, al, lane, us_w2);   // m = SiLU(W2 a + b2)
           }
-          STAMP(1);
           silu_ecl(m);
 #pragma unroll
           for (int mt = 0; mt < 4; ++mt)
@@ -1018,9 +1052,8 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
             h16_split(m, mh, ml);
             mfma_h16(a, wc1l, mh, ml, lane, us_wc1);  // SiLU(Wc1 m + bc1)
           }
-          STAMP(2);
           tail(a, r0, r1, r2, on);
-          STAMP(3);
+          STAMP(14);
         }
         // ---- flush the segment's partial sums ----
         if (P > 1) {   // wave-uniform: add the lane groups' partial sums of each receiver (DPP, fixed order)
@@ -1931,10 +1964,25 @@ int launch_layer(int n_graphs, int N, int ne, int ef_mod, const float* h, const 
       if (a.chunk_of[k] == 0xffff) a.chunk_of[k] = (unsigned short)left[i++];
     a.use_perm = 1;
   }
+  const int nw = NONODE_LAYER_WAVES ? NONODE_LAYER_WAVES : (N < 64 ? 4 : 8);
+  a.hc_n = 0;
+  if (VARIANT == EGNO && nw == 4 && cpg == 1 && NONODE_HOSTCUT) {
+    // the kernel's own derivation of a chunk's tiles and packed last tile (phase B), per chunk shape
+    const int g_last = n_graphs - (n_units - 1) * cg;
+    for (int gs : {cg, g_last}) {
+      const int rows = gs * N, ctc = (rows + 15) >> 4, Vl = rows - 16 * (ctc - 1), Nm1 = N - 1;
+      if (a.hc_n == 1 && a.hc_ctc[0] == ctc && a.hc_vl[0] == Vl) continue;
+      const int Pk = (Vl <= 4 && Nm1 >= 8) ? 4 : ((Vl <= 8 && Nm1 >= 4) ? 2 : 1);
+      const int Kp = Nm1 / Pk, Ul = Pk == 1 ? Nm1 : Kp + (Nm1 - Pk * Kp);
+      a.hc_ctc[a.hc_n] = ctc;
+      a.hc_vl[a.hc_n] = Vl;
+      unit_split<4, NONODE_TRICOST != 0>(ctc, Nm1, Ul, Pk == 1 ? Nm1 : Kp, a.hc_cut[a.hc_n]);
+      ++a.hc_n;
+    }
+  }
   ProfScope prof(VARIANT, stream);
   if (ne == 0) { a.ef = blob; a.ne = 1; a.ef_mod = 1; }   // dummy gather target; feature weights are 0
   const int kf = a.ne <= 3 ? 1 : 2;
-  const int nw = NONODE_LAYER_WAVES ? NONODE_LAYER_WAVES : (N < 64 ? 4 : 8);
   if (nw == 8) launch_cfg<VARIANT, 8>(kf, G, lds, stream, a);
   else launch_cfg<VARIANT, 4>(kf, G, lds, stream, a);
   return check_launch("egnn_layer_kernel");
@@ -2335,6 +2383,46 @@ int nonode_profile_end(float* ms_out, int* kind_out, int max_out) {
   }
   g_prof.n = 0;
   return n;
+}
+
+// Diagnostic (host only, no GPU; not part of the C ABI in nonode.h): the four-wave layer kernel's split of
+// a chunk's edge units and each wave's walk, from the very functions the kernel runs (unit_split,
+// seg_walk). The chunk has ctc tiles of Nm1 units, the last one Ul units with packed limit Ql.
+// cut[5]: wave w takes units [cut[w], cut[w + 1]). rows: per tile segment of a wave, in order,
+// {wave, tile, k_lo, k_hi, triples, pairs, singles, regular units} (8 ints; at most max_rows segments
+// are written). Returns the number of segments, or -1 for arguments the kernel never sees.
+int nonode_debug_edge_walk(int variant, int ctc, int Nm1, int Ul, int Ql, int* cut, int* rows, int max_rows) {
+  if ((variant != NONODE_VARIANT_EGNO && variant != NONODE_VARIANT_SEGNO) || ctc < 1 || ctc > 8 || Nm1 < 1 ||
+      Ul < 1 || Ul > Nm1 || Ql < 0 || Ql > Ul || !cut)
+    return -1;
+  const bool egno = variant == NONODE_VARIANT_EGNO;
+  if (egno) unit_split<4, NONODE_TRICOST != 0>(ctc, Nm1, Ul, Ql, cut);
+  else unit_split<4, false>(ctc, Nm1, Ul, Ql, cut);
+  int n = 0;
+  for (int wave = 0; wave < 4; ++wave) {
+    int u = cut[wave];
+    const int u1 = cut[wave + 1];
+    while (u < u1) {   // the kernel's segment loop
+      const int tau = imin(u / Nm1, ctc - 1);
+      const int k_lo = u - tau * Nm1 + 1;
+      const int k_hi = imin(tau == ctc - 1 ? Ul : Nm1, k_lo + (u1 - u) - 1);
+      u += k_hi - k_lo + 1;
+      const int kp_hi = imin(k_hi, tau == ctc - 1 ? Ql : Nm1);
+      const int lp = imax(kp_hi - k_lo + 1, 0);
+      const SegWalk w = egno ? seg_walk<true>(lp) : seg_walk<false>(lp);
+      if (rows && n < max_rows) {
+        const int row[8] = {wave, tau, k_lo, k_hi, w.tri, w.pair, w.one, k_hi - k_lo + 1 - lp};
+        memcpy(rows + 8 * n, row, sizeof(row));
+      }
+      ++n;
+    }
+  }
+  return n;
+}
+
+// the build's edge-walk switches: bit 0 NONODE_WALK2, 1 NONODE_TRICOST, 2 NONODE_FSPLIT, 3 NONODE_HOSTCUT
+int nonode_debug_edge_switches(void) {
+  return (NONODE_WALK2 ? 1 : 0) | (NONODE_TRICOST ? 2 : 0) | (NONODE_FSPLIT ? 4 : 0) | (NONODE_HOSTCUT ? 8 : 0);
 }
 
 #if NONODE_STAMP

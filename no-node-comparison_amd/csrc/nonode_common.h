@@ -27,6 +27,7 @@ using nonode_tu::g_err;
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef float f8 __attribute__((ext_vector_type(8)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
@@ -223,6 +224,36 @@ __device__ __forceinline__ void h16_split(const f4 (&x)[4], h8 (&hi)[2], h8 (&lo
     lo[s] = __builtin_convertvector(r, h8);
   }
 }
+// SiLU (log2 domain, see silu) of the 16 ECL pre-activations z, produced directly as the fp16x3
+// split: r = 1 / (1 + 2^z), hi = fp16(z r) and lo = fp16(fma(z, r, -hi)), each of the f32 values one
+// mixed-precision FMA (v_fma_mixlo_f16 / v_fma_mixhi_f16, v_fma_mix_f32): the f32 product z r is
+// never formed, so hi is the exact product rounded once and the residual is one f32 rounding of the
+// exact difference. For the SiLU whose only consumer is the split (the first one of the edge MLP).
+// |z r| beyond the fp16 range gives hi = +-inf and lo = -+inf exactly as h16_split does.
+// (the packed hi pair passes through an empty asm so the residuals read its halves by op_sel
+// instead of recomputing them; the asm emits nothing and constrains no MFMA operand)
+__device__ __forceinline__ void silu_split(const f4 (&z)[4], h8 (&hi)[2], h8 (&lo)[2]) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    u4 hw;
+    f8 res;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float z0 = z[2 * s + (i >> 1)][2 * (i & 1)], z1 = z[2 * s + (i >> 1)][2 * (i & 1) + 1];
+      const float r0 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z0));
+      const float r1 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z1));
+      h2 h = {(_Float16)__builtin_fmaf(z0, r0, 0.f), (_Float16)__builtin_fmaf(z1, r1, 0.f)};
+      unsigned w = __builtin_bit_cast(unsigned, h);
+      asm("" : "+v"(w));
+      h = __builtin_bit_cast(h2, w);
+      hw[i] = w;
+      res[2 * i] = __builtin_fmaf(z0, r0, -(float)h[0]);
+      res[2 * i + 1] = __builtin_fmaf(z1, r1, -(float)h[1]);
+    }
+    hi[s] = __builtin_bit_cast(h8, hw);
+    lo[s] = __builtin_convertvector(res, h8);
+  }
+}
 __device__ __forceinline__ float amax_ecl(const f4 (&x)[4]) {
   float m = 0.f;
 #pragma unroll
@@ -243,7 +274,6 @@ __device__ __forceinline__ f4 mfma16(h8 a, h8 b, f4 c) {
 // (a compiler-visible multiply, not inline asm: the hazard recognizer does not see an asm VALU
 // write, so an MFMA could read its result, or an asm could overwrite a pending MFMA's operand,
 // without the required wait states)
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ h8 h8_scale(h8 x, unsigned us) {
   const h2 sc = __builtin_bit_cast(h2, us);
   const u4 w = __builtin_bit_cast(u4, x);
@@ -467,39 +497,113 @@ __device__ __forceinline__ float group_fold(float v, int P) {
 
 // ---- balanced split of a chunk's edge units over the waves (pair mode) ----------------------------
 // A wave's range is walked tile segment by tile segment: per segment a fixed cost (tile state,
-// fragment loads, the flush), then pairs of units up to the tile's packed limit Q and single units
-// after (the pair loop's odd unit, a packed tile's regular units). Modelled costs (stamped, C3:
-// ~3.2K cycles per segment, ~6.4K per pair or single on average):
+// fragment loads, the flush), then the units up to the tile's packed limit Q by seg_walk (pairs and
+// the odd unit; EGNO: triples, then a pair or a single unit) and single units after (a packed tile's regular units).
+// Modelled costs of the pairs-and-singles walk (SEGNO; stamped, C3: ~3.2K cycles per segment, ~6.4K
+// per pair or single on average):
 constexpr int CS_SEG = 2, CS_PAIR = 4, CS_ONE = 3;
+__host__ __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
+__host__ __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
+
+// A/B switches of the EGNO four-wave edge phase. Measured on one box
+// against the parent, three alternations each: only HOSTCUT was faster; the others are off and stay
+// buildable alone.
+#ifndef NONODE_HOSTCUT
+#define NONODE_HOSTCUT 1   // the launch computes the chunk shapes' unit splits (LayerArgs::hc_cut)
+#endif
+#ifndef NONODE_WALK2
+#define NONODE_WALK2 0     // a run of 3 t + 1 >= 4 units ends in two pairs, not a triple and a single (+1.3 us)
+#endif
+#ifndef NONODE_TRICOST
+#define NONODE_TRICOST 0   // the EGNO split prices triples (same C2 cuts; +18 us when computed in the kernel)
+#endif
+#ifndef NONODE_FSPLIT
+#define NONODE_FSPLIT 0    // first SiLU rounded straight into the fp16x3 split (silu_split): -8 instructions
+#endif                     // per unit, +3.2 us
+
+// THE walk of a run of L units of a segment's packed-or-ordinary range (k <= kp_hi), shared by the
+// kernel's loops, the cost model and the host debug entry. TRIPLE (EGNO, four waves): triples while
+// they fit, then the remaining pair or single unit. (NONODE_WALK2 builds take a remainder of one unit
+// with the last triple as two pairs: 19 = 5x3 + 2x2, 4 = 2x2. Stamped, a single unit costs 3520
+// cycles, a pair 6084, a triple 8110: triple + single is the cheaper ending, and it measured so.)
+// Without TRIPLE: pairs and the odd unit.
+struct SegWalk {
+  int tri, pair, one;
+};
+template <bool TRIPLE>
+__host__ __device__ __forceinline__ SegWalk seg_walk(int L) {
+  if (L <= 0) return SegWalk{0, 0, 0};
+  if constexpr (!TRIPLE) {
+    return SegWalk{0, L >> 1, L & 1};
+  } else {
+    const int t = L / 3, r = L - 3 * t;
+    if (r == 0) return SegWalk{t, 0, 0};
+    if (r == 2) return SegWalk{t, 1, 0};
+    if (NONODE_WALK2 && t >= 1) return SegWalk{t - 1, 2, 0};
+    return SegWalk{t, 0, 1};
+  }
+}
+// Cost of the EGNO walk in units of ~760 cycles. Stamped at C2 (N = 20, 4-graph chunks of 5 full
+// tiles, four waves, 1280 chunks per launch; tools/stamp_build.sh + tools/stamp_run.py on the
+// triple-then-single walk, which has all three iteration kinds): 8110 cycles per triple, 6084 per
+// pair, 3520 per single unit, 5686 per tile segment (tile state, fragment loads, flush).
+constexpr int CT_SEG = 7, CT_TRI = 11, CT_PAIR = 8, CT_ONE = 5;
+// cost of a run of n packed-or-ordinary units. TC: the walk has triples and the model prices them
+template <bool TC>
+__host__ __device__ __forceinline__ int run_cost(int n) {
+  if constexpr (!TC) {
+    return CS_PAIR * (n >> 1) + CS_ONE * (n & 1);
+  } else {
+    const SegWalk w = seg_walk<true>(n);
+    return CT_TRI * w.tri + CT_PAIR * w.pair + CT_ONE * w.one;
+  }
+}
 // cost of units k..kend (1-based offsets) of a tile with packed limit Q
-__device__ __forceinline__ int seg_cost(int k, int kend, int Q) {
-  const int lp = max(min(kend, Q) - k + 1, 0), lr = max(kend - max(k, Q + 1) + 1, 0);
-  return CS_SEG + CS_PAIR * (lp >> 1) + CS_ONE * ((lp & 1) + lr);
+template <bool TC>
+__host__ __device__ __forceinline__ int seg_cost(int k, int kend, int Q) {
+  const int lp = imax(imin(kend, Q) - k + 1, 0), lr = imax(kend - imax(k, Q + 1) + 1, 0);
+  if constexpr (!TC) return CS_SEG + CS_PAIR * (lp >> 1) + CS_ONE * ((lp & 1) + lr);
+  else return CT_SEG + run_cost<true>(lp) + CT_ONE * lr;
 }
 // the most units from offset k on (tile of L units, packed limit Q) within budget b
-__device__ __forceinline__ int seg_take(int k, int L, int Q, int b) {
-  int bb = b - CS_SEG;
-  if (bb < CS_ONE) return 0;
-  const int lp = max(Q - k + 1, 0);
-  const int np = bb / CS_PAIR;
-  if (2 * np < lp) return 2 * np + (bb - CS_PAIR * np >= CS_ONE ? 1 : 0);
-  bb -= CS_PAIR * (lp >> 1) + CS_ONE * (lp & 1);
-  return lp + min(L - max(k, Q + 1) + 1, bb / CS_ONE);
+template <bool TC>
+__host__ __device__ __forceinline__ int seg_take(int k, int L, int Q, int b) {
+  if constexpr (!TC) {
+    int bb = b - CS_SEG;
+    if (bb < CS_ONE) return 0;
+    const int lp = imax(Q - k + 1, 0);
+    const int np = bb / CS_PAIR;
+    if (2 * np < lp) return 2 * np + (bb - CS_PAIR * np >= CS_ONE ? 1 : 0);
+    bb -= CS_PAIR * (lp >> 1) + CS_ONE * (lp & 1);
+    return lp + imin(L - imax(k, Q + 1) + 1, bb / CS_ONE);
+  } else {
+    // run_cost is non-decreasing in n (CT_ONE <= CT_PAIR <= CT_TRI <= 2 CT_PAIR) and a run of
+    // 3 (bb / CT_TRI) + 3 units costs more than bb: at most a few steps down from that bound
+    static_assert(CT_ONE <= CT_PAIR && CT_PAIR <= CT_TRI && CT_TRI <= 2 * CT_PAIR, "run_cost must be monotone");
+    int bb = b - CT_SEG;
+    if (bb < CT_ONE) return 0;
+    const int lp = imax(Q - k + 1, 0);
+    int n = imin(lp, 3 * (bb / CT_TRI) + 2);
+    while (n > 0 && run_cost<true>(n) > bb) --n;
+    if (n < lp) return n;
+    bb -= run_cost<true>(lp);
+    return lp + imin(L - imax(k, Q + 1) + 1, bb / CT_ONE);
+  }
 }
 // Contiguous ranges of the U = (ctc - 1) Nm1 + Ul units (last tile: Ul units, packed limit Ql) over
 // NW waves with the smallest modelled maximum (binary search on it, greedy fill). Wave w takes units
 // [cut[w], cut[w + 1]). Returns whether budget T fits (cut then holds the fill).
 // (cut: this wave's own LDS copy: every lane writes the same values)
-template <int NW>
-__device__ __forceinline__ bool unit_fill(int T, int ctc, int Nm1, int Ul, int Ql, int* cut) {
+template <int NW, bool TC>
+__host__ __device__ __forceinline__ bool unit_fill(int T, int ctc, int Nm1, int Ul, int Ql, int* cut) {
   int w = 0, b = T, t = 0, k = 1;
   const int U = (ctc - 1) * Nm1 + Ul;
   cut[0] = 0;
   while (t < ctc) {
     const int L = t == ctc - 1 ? Ul : Nm1, Q = t == ctc - 1 ? Ql : Nm1;
-    const int n = seg_take(k, L, Q, b);
+    const int n = seg_take<TC>(k, L, Q, b);
     if (k + n - 1 == L) {
-      b -= seg_cost(k, L, Q);
+      b -= seg_cost<TC>(k, L, Q);
       ++t;
       k = 1;
     } else {
@@ -512,16 +616,16 @@ __device__ __forceinline__ bool unit_fill(int T, int ctc, int Nm1, int Ul, int Q
   for (int i = w + 1; i <= NW; ++i) cut[i] = U;
   return true;
 }
-template <int NW>
-__device__ __forceinline__ void unit_split(int ctc, int Nm1, int Ul, int Ql, int* cut) {
+template <int NW, bool TC = false>
+__host__ __device__ __forceinline__ void unit_split(int ctc, int Nm1, int Ul, int Ql, int* cut) {
   int lo = 0, hi = 0;
-  for (int t = 0; t < ctc; ++t) hi += seg_cost(1, t == ctc - 1 ? Ul : Nm1, t == ctc - 1 ? Ql : Nm1);
+  for (int t = 0; t < ctc; ++t) hi += seg_cost<TC>(1, t == ctc - 1 ? Ul : Nm1, t == ctc - 1 ? Ql : Nm1);
   while (lo < hi) {   // smallest T that fits
     const int mid = (lo + hi) >> 1;
-    if (unit_fill<NW>(mid, ctc, Nm1, Ul, Ql, cut)) hi = mid;
+    if (unit_fill<NW, TC>(mid, ctc, Nm1, Ul, Ql, cut)) hi = mid;
     else lo = mid + 1;
   }
-  unit_fill<NW>(lo, ctc, Nm1, Ul, Ql, cut);
+  unit_fill<NW, TC>(lo, ctc, Nm1, Ul, Ql, cut);
 }
 // max over the 4 lane groups (the column max of an ECL activation)
 __device__ __forceinline__ float group_max(float v) {

@@ -10,8 +10,9 @@ import bench  # noqa: E402
 import no_node_comparison_amd as pkg  # noqa: E402
 from no_node_comparison_amd import _lib  # noqa: E402
 
-NAMES = {0: "B head", 1: "B silu/split/mfma W2", 2: "B silu/split/mfma Wc1", 3: "B tail", 6: "A work",
-         7: "A barrier", 8: "B segment prologue", 9: "B flush", 10: "B end (last seg)", 11: "B barrier",
+NAMES = {0: "B pair head", 1: "B pair silu/split/mfma W2", 2: "B pair silu/split/mfma Wc1", 3: "B pair tail",
+         4: "B triple iteration", 5: "B segment prologue", 14: "B single unit", 6: "A work",
+         7: "A barrier", 8: "B singles prologue", 9: "B flush", 10: "B end (last seg)", 11: "B barrier",
          12: "C work", 13: "C barrier"}
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
@@ -33,3 +34,15 @@ for i in range(16):
     if buf[i]:
         print(f"{i:2d} {NAMES.get(i, '?'):28s} {buf[i] / launches / waves:10.0f} cyc/wave/launch  {buf[i] / tot:6.1%}")
 print(f"   total {tot / launches / waves:.0f} cyc/wave/launch")
+# cycles per iteration of the edge walk (the constants of the split's cost model, nonode_common.h):
+# the walk of this build's C2 chunk (4 graphs, 5 full tiles of 19 units) from the library itself
+cut = (ctypes.c_int * 5)()
+rows = (ctypes.c_int * (8 * 64))()
+nseg = L.nonode_debug_edge_walk(0, 5, 19, 19, 19, cut, rows, 64)
+tri, pair, one = (sum(rows[8 * i + j] for i in range(nseg)) for j in (4, 5, 6))
+chunks = launches * (512 * 10 // 4)
+print(f"   C2 chunk: cuts {list(cut)}, {nseg} segments, {tri} triples, {pair} pairs, {one} singles")
+for name, cyc, n in (("segment (prologue + flush)", buf[5] + buf[8] + buf[9], nseg), ("triple", buf[4], tri),
+                     ("pair", buf[0] + buf[1] + buf[2] + buf[3], pair), ("single", buf[14], one)):
+    if n:
+        print(f"   {name:28s} {cyc / chunks / n:8.0f} cycles each")
