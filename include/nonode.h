@@ -16,7 +16,8 @@
  *   edge features   [n_graphs_ef * N*(N-1)][n_edge_feat] in the reference edge order
  *                   (b, i, j != i)  (EGNO/simulation/dataset_simple.py:64-71,101-111)
  *   graphs          fully connected, equal size N, no self loops; row = receiver i,
- *                   col = sender j (basic.py:168-186, gcl.py:111-119)
+ *                   col = sender j (basic.py:168-186, gcl.py:111-119). The *_graph entries at the
+ *                   end take any edge list instead, as a CSR by receiver (inference).
  */
 #ifndef NONODE_H_
 #define NONODE_H_
@@ -535,6 +536,72 @@ int nonode_check_full_edges(const void* rows, const void* cols, int idx_bytes, l
 /* If *flag is set when the launch runs, fill bufs[k][0..counts[k]) (k < n_bufs <= 4, fp32) with NaN:
  * the outputs of a forward whose edge list failed nonode_check_full_edges. */
 int nonode_poison_if_flagged(const int* flag, int n_bufs, float* const* bufs, const long long* counts, void* stream);
+
+
+/* ---- arbitrary edge lists: CSR graph kernels (inference) ---- */
+
+/*
+ * The `edges` argument of EGNN_Layer.forward (basic.py:167-186, aggregate basic.py:6-31) and
+ * SEGNO_GCL.forward (gcl.py:111-119, unsorted_segment_mean) as a CSR by receiver, built on the device:
+ * rows (receivers), cols (senders): E indices of idx_bytes = 4 or 8 bytes, E < 2^31. Writes
+ * row_ptr [n_nodes + 1], col [E], eid [E] (original edge index), all int32. Within a receiver the
+ * edges are ordered by (sender, original index), so the CSR is a pure function of the edge set. Self
+ * loops and duplicate edges are kept (the reference sums them). An index outside [0, n_nodes) sets the
+ * device int *flag to 1 (never to 0) and that edge is dropped: row_ptr[n_nodes] counts the kept edges,
+ * and nothing downstream reads an index that was not range-checked. E = 0 is legal.
+ * Workspace: nonode_graph_workspace_bytes(E, n_nodes).
+ */
+size_t nonode_graph_workspace_bytes(long long E, int n_nodes);
+int nonode_graph_build(const void* rows, const void* cols, int idx_bytes, long long E, int n_nodes, int* row_ptr,
+                       int* col, int* eid, int* flag, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * nonode_egnn_layer on an explicit edge list: EGNN_Layer.forward (basic.py:167-186) for variant EGNO,
+ * SEGNO_GCL.forward (gcl.py:111-119) for variant SEGNO, over n_frames copies of one n_nodes-node graph
+ * given as the CSR of nonode_graph_build. Frame f owns node rows f*n_nodes .. of h [.][64], x, v [.][3]
+ * (EGNO's T-fold replication, egno.py:84-96); its edge features are block f % ef_frames of edge_fea
+ * [ef_frames][E][n_edge_feat], read at eid. blob from nonode_pack_layer (its NORM_RADIAL / TANH_COORD
+ * flags are followed). A node without incoming edges gets zero message and force sums and the mean's
+ * count.clamp(min=1) (basic.py:28, gcl.py unsorted_segment_mean). dt, coords_weight, recurrent, v_out
+ * as nonode_egnn_layer. Per-receiver sums are added in CSR order without float atomics: bitwise
+ * reproducible. Workspace: nonode_egnn_layer_graph_workspace_bytes(n_frames, n_nodes).
+ */
+size_t nonode_egnn_layer_graph_workspace_bytes(int n_frames, int n_nodes);
+int nonode_egnn_layer_graph(int variant, int n_frames, int n_nodes, long long E, int n_edge_feat, int ef_frames,
+                            const float* h, const float* x, const float* v, const float* edge_fea, const float* blob,
+                            const int* row_ptr, const int* col, const int* eid, float dt, float coords_weight,
+                            int recurrent, float* h_out, float* x_out, float* v_out, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/*
+ * EGNO.forward (EGNO/model/egno.py:37-111) on an explicit edge list: the arguments of
+ * nonode_egno_forward_flat with (B, N) replaced by n_nodes, E and the CSR, and blobs from
+ * nonode_pack_layer. t_in = NULL: the single-input layout of nonode_egno_forward (x, v, loc_mean
+ * [n_nodes][3], h [n_nodes][in_node], edge_fea [E][n_edge_feat]); otherwise the per-frame layout of
+ * nonode_egno_forward_frames ([T*n_nodes] rows, edge_fea [T][E][n_edge_feat]). tconv_blobs = tconvx_w
+ * = NULL: use_time_conv=False. Outputs [T*n_nodes] rows, time-major. n_nodes % Bt == 0.
+ * Workspace: nonode_egno_graph_workspace_bytes(n_nodes, T, Bt).
+ */
+size_t nonode_egno_graph_workspace_bytes(int n_nodes, int T, int Bt);
+int nonode_egno_forward_graph(int n_nodes, long long E, int T, int n_layers, int in_node, int n_edge_feat,
+                              int time_emb_dim, int modes, int Bt, const float* x, const float* h, const float* v,
+                              const float* loc_mean, const float* edge_fea, const float* t_in, const float* t_out,
+                              const float* emb_w, const float* emb_b, const float* const* blobs,
+                              const float* const* tconv_blobs, const float* const* tconvx_w, const int* row_ptr,
+                              const int* col, const int* eid, float* x_out, float* v_out, float* h_out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * SEGNO.embedding + SEGNO.forward_step (SEGNO/models/model.py:73,95-102) on an explicit edge list: the
+ * arguments of nonode_segno_forward_step with (B, N) replaced by n_nodes, E and the CSR; edge_attr
+ * [E][n_edge_feat] is frozen over the T substeps. Workspace: nonode_segno_graph_workspace_bytes(n_nodes).
+ */
+size_t nonode_segno_graph_workspace_bytes(int n_nodes);
+int nonode_segno_forward_step_graph(int n_nodes, long long E, int T, int in_node, int n_edge_feat, const float* his,
+                                    const float* h_in, const float* x, const float* v, const float* edge_attr,
+                                    const float* emb_w, const float* emb_b, const float* blob, const int* row_ptr,
+                                    const int* col, const int* eid, float coords_weight, int recurrent, float* x_out,
+                                    float* v_out, float* h_out, void* workspace, size_t workspace_bytes, void* stream);
 
 
 /* ---- rollout metrics ---- */

@@ -37,6 +37,9 @@ SYMBOLS = (
     "nonode_pack_layer_flat_bwd", "nonode_egnn_layer_flat_bwd_node_floats", "nonode_egnn_layer_flat_bwd_edge_floats",
     "nonode_egnn_layer_flat_bwd",
     "nonode_egno_backward_inputs", "nonode_prepare_inputs_bwd",
+    "nonode_graph_workspace_bytes", "nonode_graph_build", "nonode_egnn_layer_graph_workspace_bytes",
+    "nonode_egnn_layer_graph", "nonode_egno_graph_workspace_bytes", "nonode_egno_forward_graph",
+    "nonode_segno_graph_workspace_bytes", "nonode_segno_forward_step_graph",
 )
 
 VARIANT_EGNO = 0
@@ -227,6 +230,21 @@ def lib():
     L.nonode_egnn_layer_flat_bwd_edge_floats.argtypes = [_i, _i]
     L.nonode_egnn_layer_flat_bwd_edge_floats.restype = _sz
     L.nonode_egnn_layer_flat_bwd.argtypes = [_i] * 4 + [_vp] * 14
+    L.nonode_graph_workspace_bytes.argtypes = [_ll, _i]
+    L.nonode_graph_workspace_bytes.restype = _sz
+    L.nonode_graph_build.argtypes = [_vp, _vp, _i, _ll, _i] + [_vp] * 5 + [_sz, _vp]
+    L.nonode_egnn_layer_graph_workspace_bytes.argtypes = [_i, _i]
+    L.nonode_egnn_layer_graph_workspace_bytes.restype = _sz
+    L.nonode_egnn_layer_graph.argtypes = ([_i] * 3 + [_ll, _i, _i] + [_vp] * 8 + [_f, _f, _i] + [_vp] * 4
+                                          + [_sz, _vp])
+    L.nonode_egno_graph_workspace_bytes.argtypes = [_i, _i, _i]
+    L.nonode_egno_graph_workspace_bytes.restype = _sz
+    L.nonode_egno_forward_graph.argtypes = ([_i, _ll] + [_i] * 7 + [_vp] * 9 + [ctypes.POINTER(_vp)] * 3
+                                            + [_vp] * 7 + [_sz, _vp])
+    L.nonode_segno_graph_workspace_bytes.argtypes = [_i]
+    L.nonode_segno_graph_workspace_bytes.restype = _sz
+    L.nonode_segno_forward_step_graph.argtypes = ([_i, _ll, _i, _i, _i] + [_vp] * 11 + [_f, _i] + [_vp] * 4
+                                                  + [_sz, _vp])
     L.nonode_profile_begin.argtypes = [_i]
     L.nonode_profile_end.argtypes = [ctypes.POINTER(_f), ctypes.POINTER(_i), _i]
     for s in SYMBOLS:

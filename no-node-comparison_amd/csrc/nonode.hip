@@ -2352,6 +2352,133 @@ int nonode_segno_forward_step(int B, int N, int T, int in_node, int n_edge_feat,
                              recurrent, h_out, x_out, v_out, s, T, pp);
 }
 
+// ---- whole models on an explicit edge list (host glue; the layer kernels live in nonode_graph.hip) ----
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+size_t nonode_egno_graph_workspace_bytes(int n_nodes, int T, int Bt) {
+  if (n_nodes <= 0 || T <= 0 || Bt <= 0) return 0;
+  return align256(nonode_egno_workspace_bytes(1, n_nodes, T, Bt)) +
+         nonode_tu::graph_layer_ws_floats((long long)n_nodes * T) * sizeof(float);
+}
+
+int nonode_egno_forward_graph(int n_nodes, long long E, int T, int n_layers, int in_node, int n_edge_feat,
+                              int time_emb_dim, int modes, int Bt, const float* x, const float* h, const float* v,
+                              const float* loc_mean, const float* edge_fea, const float* t_in, const float* t_out,
+                              const float* emb_w, const float* emb_b, const float* const* blobs,
+                              const float* const* tconv_blobs, const float* const* tconvx_w, const int* row_ptr,
+                              const int* col, const int* eid, float* x_out, float* v_out, float* h_out,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  if (n_nodes <= 0 || E < 0 || T <= 0 || T > TMAX || n_layers < 1 || in_node < 0 || in_node > 8 || modes < 1 ||
+      modes > MMAX || time_emb_dim < 4 || time_emb_dim > 64 || (time_emb_dim & 1) || Bt <= 0 || n_nodes % Bt != 0 ||
+      n_edge_feat < 0 || n_edge_feat > 4)
+    return fail(NONODE_EUNSUPPORTED, "egno_forward_graph: n_nodes=%d E=%lld T=%d layers=%d in_node=%d modes=%d temb=%d Bt=%d",
+                n_nodes, E, T, n_layers, in_node, modes, time_emb_dim, Bt);
+  const bool tc = tconv_blobs != nullptr;
+  if (!x || !h || !v || (tc && !loc_mean) || !t_out || !emb_w || !emb_b || !blobs || tc != (tconvx_w != nullptr) ||
+      !row_ptr || (E > 0 && (!col || !eid || (n_edge_feat > 0 && !edge_fea))) || !x_out || !v_out || !h_out || !workspace)
+    return fail(NONODE_EINVAL, "egno_forward_graph: null pointer");
+  if (workspace_bytes < nonode_egno_graph_workspace_bytes(n_nodes, T, Bt))
+    return fail(NONODE_EINVAL, "egno_forward_graph: workspace %zu < %zu", workspace_bytes,
+                nonode_egno_graph_workspace_bytes(n_nodes, T, Bt));
+  hipStream_t s = (hipStream_t)stream;
+  const int BN = n_nodes, frames = t_in ? 1 : 0;
+  const size_t n = (size_t)BN * T;
+  float* hB = (float*)workspace;
+  float* xB = hB + n * 64;
+  float* etab = xB + n * 3;
+  float* lws = (float*)((char*)workspace + align256(nonode_egno_workspace_bytes(1, n_nodes, T, Bt)));
+  const int emb_ld = in_node + (t_in ? 2 : 1) * time_emb_dim;
+  // frame f owns node rows f n_nodes .. and shares the one CSR (egno.py:84-96); v is unchanged by the layer
+  auto layer = [&](int l, const float* hi, const float* xi, float* ho, float* xo) {
+    return nonode_tu::graph_layer(NONODE_VARIANT_EGNO, T, n_nodes, E, n_edge_feat, frames ? T : 1, hi, xi, v_out,
+                                  edge_fea, blobs[l], row_ptr, col, eid, 0.f, 1.f, 0, ho, xo, nullptr, lws, s);
+  };
+  hipLaunchKernelGGL(temb_kernel, dim3((Bt * T + TEMB_ROWS - 1) / TEMB_ROWS), dim3(256), 0, s, Bt, T, in_node,
+                     time_emb_dim, t_out, emb_w, emb_ld, emb_b, etab, t_in);
+  if (int rc = check_launch("temb_kernel")) return rc;
+  if (!tc) {   // as egno_forward_impl: layer l reads buffer (L - l) & 1 and writes (L - 1 - l) & 1
+    float* hb[2] = {h_out, hB};
+    float* xb[2] = {x_out, xB};
+    const int L = n_layers;
+    hipLaunchKernelGGL(h0_kernel, dim3((BN * 64 + 255) / 256), dim3(256), 0, s, BN, T, in_node, Bt, h, emb_w, emb_ld,
+                       etab, x, v, hb[L & 1], xb[L & 1], v_out, frames);
+    if (int rc = check_launch("h0_kernel")) return rc;
+    for (int l = 0; l < L; ++l) {
+      const int i = (L - l) & 1, o = (L - 1 - l) & 1;
+      if (int rc = layer(l, hb[i], xb[i], hb[o], xb[o])) return rc;
+    }
+    return NONODE_OK;
+  }
+  for (int l = 0; l < n_layers; ++l) {
+    TconvArgs a{};
+    a.BN = BN; a.T = T; a.M = effective_modes(T, modes); a.Mfull = modes;
+    a.wp = tconv_blobs[l]; a.wx = tconvx_w[l]; a.frames = frames;
+    a.h_out = hB; a.x_out = xB; a.v_out = v_out;
+    if (l == 0) {
+      a.h = nullptr; a.x = x; a.v = v; a.lm = loc_mean;
+      a.hin = h; a.din = in_node; a.emb_w = emb_w; a.emb_ld = emb_ld; a.etab = etab; a.Bt = Bt;
+    } else {
+      a.h = h_out; a.x = x_out; a.v = v_out; a.lm = loc_mean;
+    }
+    if (int rc = launch_tconv(l == 0, a, s)) return rc;
+    if (int rc = layer(l, hB, xB, h_out, x_out)) return rc;
+  }
+  return NONODE_OK;
+}
+
+size_t nonode_segno_graph_workspace_bytes(int n_nodes) {
+  if (n_nodes <= 0) return 0;
+  return align256(nonode_segno_workspace_bytes(1, n_nodes)) + nonode_tu::graph_layer_ws_floats(n_nodes) * sizeof(float);
+}
+
+int nonode_segno_forward_step_graph(int n_nodes, long long E, int T, int in_node, int n_edge_feat, const float* his,
+                                    const float* h_in, const float* x, const float* v, const float* edge_attr,
+                                    const float* emb_w, const float* emb_b, const float* blob, const int* row_ptr,
+                                    const int* col, const int* eid, float coords_weight, int recurrent, float* x_out,
+                                    float* v_out, float* h_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (n_nodes <= 0 || E < 0 || T < 0 || in_node < 0 || in_node > 8 || n_edge_feat < 0 || n_edge_feat > 4)
+    return fail(NONODE_EUNSUPPORTED, "segno_forward_step_graph: n_nodes=%d E=%lld T=%d in_node=%d ne=%d", n_nodes, E, T,
+                in_node, n_edge_feat);
+  if (!x || !v || !blob || !row_ptr || (E > 0 && (!col || !eid || (n_edge_feat > 0 && !edge_attr))) || !x_out ||
+      !v_out || !h_out || !workspace || (!h_in && (!his || !emb_w || !emb_b)))
+    return fail(NONODE_EINVAL, "segno_forward_step_graph: null pointer");
+  if (workspace_bytes < nonode_segno_graph_workspace_bytes(n_nodes))
+    return fail(NONODE_EINVAL, "segno_forward_step_graph: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)n_nodes;
+  float* hemb = (float*)workspace;
+  float* pph[2] = {hemb + n * 64, hemb + 2 * n * 64};
+  float* ppx[2] = {hemb + 3 * n * 64, hemb + 3 * n * 64 + n * 3};
+  float* ppv[2] = {hemb + 3 * n * 64 + 2 * n * 3, hemb + 3 * n * 64 + 3 * n * 3};
+  float* lws = (float*)((char*)workspace + align256(nonode_segno_workspace_bytes(1, n_nodes)));
+  const float* hc = h_in;
+  if (!hc) {
+    hipLaunchKernelGGL(embed_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, s, n_nodes, in_node, his,
+                       emb_w, emb_b, hemb);
+    if (int rc = check_launch("embed_kernel")) return rc;
+    hc = hemb;
+  }
+  if (T == 0) {
+    hipMemcpyAsync(h_out, hc, n * 64 * sizeof(float), hipMemcpyDeviceToDevice, s);
+    hipMemcpyAsync(x_out, x, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s);
+    hipMemcpyAsync(v_out, v, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s);
+    return check_launch("segno T=0 copy");
+  }
+  // T substeps of the shared layer with the edge attributes frozen (model.py:95-102), dt = 1/T
+  const float* hi = hc; const float* xi = x; const float* vi = v;
+  for (int t = 0; t < T; ++t) {
+    const bool last = t == T - 1;
+    float* ho = last ? h_out : pph[t & 1];
+    float* xo = last ? x_out : ppx[t & 1];
+    float* vo = last ? v_out : ppv[t & 1];
+    if (int rc = nonode_tu::graph_layer(NONODE_VARIANT_SEGNO, 1, n_nodes, E, n_edge_feat, 1, hi, xi, vi, edge_attr, blob,
+                                        row_ptr, col, eid, 1.0f / (float)T, coords_weight, recurrent, ho, xo, vo, lws, s))
+      return rc;
+    hi = ho; xi = xo; vi = vo;
+  }
+  return NONODE_OK;
+}
+
 int nonode_profile_begin(int max_records) {
   std::lock_guard<std::mutex> lk(g_prof.mu);
   if (max_records <= 0 || max_records > (1 << 20)) return fail(NONODE_EINVAL, "profile_begin: %d", max_records);

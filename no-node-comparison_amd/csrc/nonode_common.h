@@ -19,6 +19,13 @@
 
 namespace nonode_tu {
 extern thread_local std::string g_err;   // nonode_last_error(); defined in nonode.hip
+// the general-graph layer (nonode_graph.hip), for the whole-model entries' host glue in nonode.hip:
+// three launches on `s`; ws holds graph_layer_ws_floats(n_frames n_nodes) floats
+size_t graph_layer_ws_floats(long long n_total);
+int graph_layer(int variant, int n_frames, int n_nodes, long long E, int ne, int ef_frames, const float* h,
+                const float* x, const float* v, const float* ef, const float* blob, const int* row_ptr,
+                const int* col, const int* eid, float dt, float cw, int recurrent, float* h_out, float* x_out,
+                float* v_out, float* ws, hipStream_t s);
 }
 
 namespace {

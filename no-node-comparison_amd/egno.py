@@ -12,6 +12,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from . import graph as _graph
 from .graph import check_full_graph, finish
 
 
@@ -87,12 +88,20 @@ class EGNO(nn.Module):
     wide with Tanh, basic.py:38-40; main_simulation_simple_no.py --flat) runs forward on its own layer
     kernels (csrc/nonode_flat.hip); its training (num_inputs=1) runs one autograd node per layer
     (autograd.FlatLayerTrain: HIP reverse kernels write the operands, weight gradients are GEMMs).
+
+    graph (keyword, not in the reference): "full" (default) takes exactly the dataset's fully connected,
+    equal-size batch, as the fused kernels index it; "any" also takes every other edge list (inference
+    only, not with flat=True) on the CSR graph kernels (csrc/nonode_graph.hip), while a list already
+    known to be the full one keeps the fused path.
     """
 
     def __init__(self, n_layers, in_node_nf, in_edge_nf, hidden_nf, activation=nn.SiLU(), device='cpu',
                  with_v=False, flat=False, norm=False, use_time_conv=True, num_modes=2, num_timesteps=8,
-                 time_emb_dim=32, num_inputs=1, varDT=False, fix_out_size=False):
+                 time_emb_dim=32, num_inputs=1, varDT=False, fix_out_size=False, *, graph="full"):
         super().__init__()
+        if graph not in ("full", "any"):
+            raise ValueError(f'graph must be "full" or "any", got {graph!r}')
+        self.graph = graph
         unsupported = []
         if num_inputs < 1:
             unsupported.append(f"num_inputs={num_inputs}")
@@ -272,6 +281,8 @@ class EGNO(nn.Module):
         tapes = self._tapes(x, h, v, loc_mean)
         if self.flat and tapes and self.num_inputs > 1:
             raise NotImplementedError("EGNO(flat=True) training runs the single-input model (num_inputs=1)")
+        if self._general(edge_index, h.shape[-2], tapes):
+            return self._forward_graph(x, h, edge_index, edge_fea, v, loc_mean, timesteps_in, timesteps_out)
         if self.num_inputs > 1:
             return self._forward_multi(x, h, edge_index, edge_fea, v, loc_mean, timesteps_in, timesteps_out)
         _lib.require_device(x, h, v, loc_mean, edge_fea, self.embedding.weight)
@@ -294,6 +305,72 @@ class EGNO(nn.Module):
             from .autograd import egno_forward_train
             return finish(egno_forward_train(self, x, h, edge_fea, v, loc_mean, timesteps_out, B, N))
         return finish(self._forward_kernels(x, h, edge_fea, v, loc_mean, timesteps_out, B, N))
+
+    def _general(self, edge_index, n_nodes, tapes):
+        """Whether this forward takes the general-graph path (graph="any" and an edge list not already
+        known to be the fully connected one). Inference only: refused before any device work otherwise."""
+        if self.graph != "any" or _graph.known_full(edge_index, n_nodes) is not None:
+            return False
+        if tapes:
+            raise NotImplementedError("general graphs: inference only")
+        if self.flat:
+            raise NotImplementedError("general graphs: inference only, and not with flat=True")
+        _graph.check_host_range(edge_index, n_nodes)
+        return True
+
+    @torch.no_grad()
+    def _forward_graph(self, x, h, edge_index, edge_fea, v, loc_mean, timesteps_in, timesteps_out):
+        """egno.py:37-111 on any edge list (graph="any"): nonode_egno_forward_graph over the CSR of
+        graph.csr. Single input: x, v, loc_mean [n, 3], h [n, F], edge_fea [E, in_edge_nf]; num_inputs = I
+        > 1: the shapes of _forward_multi with edge_fea [I, E, in_edge_nf]."""
+        I, T = self.num_inputs, self.num_timesteps
+        multi = I > 1
+        _lib.require_device(x, h, v, loc_mean, edge_fea, timesteps_in if multi else None, self.embedding.weight)
+        n = h.shape[-2]
+        E = _graph._split(edge_index)[0].numel()
+        if timesteps_out is None:
+            timesteps_out = torch.arange(T, device=x.device).unsqueeze(0)
+        if timesteps_out.dim() != 2 or timesteps_out.shape[1] != T:
+            raise ValueError(f"timesteps_out must be [B, {T}], got {tuple(timesteps_out.shape)}")
+        Bt = timesteps_out.shape[0]
+        if n % Bt:
+            raise ValueError("number of nodes must be a multiple of timesteps_out.shape[0] (egno.py:66)")
+        f32 = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()  # noqa: E731
+        t_in = None
+        if multi:
+            if x.dim() != 3 or x.shape[0] != I or h.dim() != 3 or h.shape[0] != I:
+                raise ValueError(f"num_inputs={I}: x, v, loc_mean must be [{I}, BN, 3] and h [{I}, BN, F]")
+            if timesteps_in is None or timesteps_in.dim() != 2 or timesteps_in.shape != (Bt, I):
+                raise ValueError(f"num_inputs={I}: timesteps_in must be [{Bt}, {I}]")
+            if edge_fea.shape != (I, E, self.in_edge_nf):
+                raise ValueError(f"edge_fea must be [{I}, {E}, {self.in_edge_nf}], got {tuple(edge_fea.shape)}")
+            fidx = torch.tensor(self.frame_inputs(T), device=x.device)
+            per_frame = lambda t: None if t is None else f32(t)[fidx].reshape(T * t.shape[1], t.shape[2]).contiguous()  # noqa: E731,E501
+            x, h, v, lm, ef = (per_frame(t) for t in (x, h, v, loc_mean, edge_fea))
+            t_in = f32(timesteps_in)[:, fidx].contiguous()
+            tt = f32(timesteps_out)
+        else:
+            if edge_fea.shape != (E, self.in_edge_nf):
+                raise ValueError(f"edge_fea must be [{E}, {self.in_edge_nf}], got {tuple(edge_fea.shape)}")
+            x, h, v, lm, ef = f32(x), f32(h), f32(v), f32(loc_mean), f32(edge_fea)
+            tt = self._t_out_f32(timesteps_out)
+        row_ptr, col, eid = _graph.csr(edge_index, n, device=x.device)
+        blobs, tblobs = self._packed()
+        dev = x.device
+        x_out = torch.empty(T * n, 3, device=dev)
+        v_out = torch.empty(T * n, 3, device=dev)
+        h_out = torch.empty(T * n, self.hidden_nf, device=dev)
+        L = _lib.lib()
+        ws_bytes = L.nonode_egno_graph_workspace_bytes(n, T, Bt)
+        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev)
+        blob_p, (tcw_p, tcx_p, _keep) = self._launch_arrays(blobs, tblobs)
+        ew, eb = f32(self.embedding.weight), f32(self.embedding.bias)
+        _lib.check(L.nonode_egno_forward_graph(
+            n, E, T, self.n_layers, self.in_node_nf, self.in_edge_nf, self.time_emb_dim, self.num_modes, Bt,
+            _lib.ptr(x), _lib.ptr(h), _lib.ptr(v), _lib.ptr(lm), _lib.ptr(ef), _lib.ptr(t_in), _lib.ptr(tt),
+            _lib.ptr(ew), _lib.ptr(eb), blob_p, tcw_p, tcx_p, _lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(eid),
+            _lib.ptr(x_out), _lib.ptr(v_out), _lib.ptr(h_out), _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
+        return finish((x_out, v_out, h_out))
 
     def _trains(self):
         """Training forward: train mode, gradients enabled and a parameter that requires grad."""

@@ -16,6 +16,12 @@ exactly it.
   forward's outputs are NaN, and the error is raised one call later at most.
 - Edge lists made by ``full_edges`` on the device (the ``get_edges`` counterpart, one kernel) are valid
   by construction and enter the cache without a check.
+
+General graphs (``EGNO`` / ``SEGNO`` with ``graph="any"``, inference): any other edge list becomes a CSR
+by receiver (``csr``, one ``nonode_graph_build`` per edge tensor pair, cached the same way), which the
+graph kernels of csrc/nonode_graph.hip walk. An index outside [0, n_nodes) raises ValueError at once for a
+host list; for a device list it goes through the same flag / ``finish()`` / deferred ValueError mechanism,
+with ``nonode_graph_build`` as the flag's writer (it drops the bad edge, so no kernel reads out of range).
 """
 from collections import OrderedDict
 
@@ -77,6 +83,12 @@ def _split(edge_index):
 
 _NOT_FULL = ("edge_index is not the dataset's fully connected edge list (receiver i, sender j != i, ordered "
              "by sample, i, j); the MI355X kernels index that pattern implicitly")
+_BAD_INDEX = "edge_index holds a node index outside [0, n_nodes)"
+
+# general graphs (EGNO / SEGNO graph="any"): the CSR by receiver of an edge tensor pair, built once
+# per pair on the device and cached under the keys of _checked, with the same bound; each entry holds
+# a reference to the edge tensors for the same reason
+_csr = OrderedDict()
 
 
 class _DeviceChecks:
@@ -88,6 +100,7 @@ class _DeviceChecks:
         self.event = None      # recorded after the flag's copy to self.host
         self.in_flight = []    # cache keys whose checks that copy covers
         self.unconfirmed = []  # cache keys checked after it (not covered by a copy yet)
+        self.csr_keys = set()  # those of them whose flag writer is nonode_graph_build (csr below)
 
     def pending(self):
         return bool(self.in_flight or self.unconfirmed)
@@ -103,16 +116,21 @@ class _DeviceChecks:
         bad = int(self.host[0]) != 0
         self.event = None
         if not bad:
+            self.csr_keys.difference_update(self.in_flight)
             self.in_flight = []
             return
         # which of the checked lists failed is not known: forget every unconfirmed one (a later use
         # re-checks it), clear the flag behind the checks already launched, report
-        for k in self.in_flight + self.unconfirmed:
+        keys = self.in_flight + self.unconfirmed
+        for k in keys:
             _checked.pop(k, None)
+            _csr.pop(k, None)
         self.in_flight, self.unconfirmed = [], []
         self.flag.zero_()
         self.host.zero_()
-        raise ValueError(_NOT_FULL + " (found by the device-side check of an earlier call, whose outputs "
+        what = _NOT_FULL if not any(k in self.csr_keys for k in keys) else _BAD_INDEX
+        self.csr_keys.clear()
+        raise ValueError(what + " (found by the device-side check of an earlier call, whose outputs "
                          "were filled with NaN)")
 
     def launch(self, rows, cols, E, B, N):
@@ -204,3 +222,74 @@ def sync_checks(device=None):
         if st.unconfirmed:        # checks launched after the last copy: copy the flag once more
             st.finish(())
             st.poll(block=True)
+
+
+# ---- general graphs: any edge list, as a CSR by receiver ----
+
+def known_full(edge_index, n_nodes):
+    """(B, N) if this very edge tensor pair is already known to be the fully connected list (a hit in
+    the cache of check_full_graph, which lists made by full_edges on the device enter), else None."""
+    rows, cols = _split(edge_index)
+    hit = _checked.get(_key(rows, cols, rows.numel(), n_nodes))
+    return None if hit is None else (hit[0], hit[1])
+
+
+def check_host_range(edge_index, n_nodes):
+    """Host (CPU) edge tensors: ValueError at once for an index outside [0, n_nodes). Device tensors
+    are range-checked by nonode_graph_build (csr), without blocking the host."""
+    rows, cols = _split(edge_index)
+    if cols.numel() != rows.numel() or rows.dim() != 1 or cols.dim() != 1:
+        raise ValueError("edge_index rows and cols must be 1-D tensors of one length")
+    if rows.device != cols.device:
+        raise ValueError("edge_index rows and cols must be on one device")
+    if not rows.is_cuda and rows.numel():
+        lo = min(int(rows.min()), int(cols.min()))
+        hi = max(int(rows.max()), int(cols.max()))
+        if lo < 0 or hi >= n_nodes:
+            raise ValueError(_BAD_INDEX + f": found {lo if lo < 0 else hi} with n_nodes = {n_nodes}")
+
+
+def csr(edge_index, n_nodes, device=None):
+    """(row_ptr [n_nodes + 1], col [E], eid [E]) int32 device tensors: the edge list (row = receiver,
+    col = sender, any topology; self loops and duplicate edges kept) as a CSR by receiver, each row
+    ordered by (sender, original index), so the result is a pure function of the edge set. One
+    nonode_graph_build per edge tensor pair (cached like check_full_graph's verdicts). A host list is
+    checked on the spot (ValueError) and copied to `device` (default: the current ROCm device); a device
+    list with an index outside [0, n_nodes) has that edge dropped, the device flag set (finish() then
+    NaN-fills the forward's outputs) and ValueError raised by a later call or sync_checks()."""
+    rows, cols = _split(edge_index)
+    check_host_range(edge_index, n_nodes)
+    E = rows.numel()
+    if n_nodes <= 0 or E >= 2 ** 31:
+        raise ValueError(f"csr: n_nodes = {n_nodes}, E = {E} (n_nodes >= 1, E < 2^31)")
+    dev = rows.device if rows.is_cuda else torch.device(device if device is not None else "cuda")
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    st = _state(dev)
+    st.poll()
+    key = _key(rows, cols, E, n_nodes) + (str(dev),)
+    hit = _csr.get(key)
+    if hit is not None:
+        _csr.move_to_end(key)
+        return hit[0], hit[1], hit[2]
+    from . import _lib
+    r, c = rows, cols
+    if r.dtype != c.dtype or r.dtype not in (torch.int32, torch.int64):
+        r, c = r.to(torch.int64), c.to(torch.int64)
+    r, c = r.to(dev).contiguous(), c.to(dev).contiguous()
+    row_ptr = torch.empty(n_nodes + 1, dtype=torch.int32, device=dev)
+    col = torch.empty(E, dtype=torch.int32, device=dev)
+    eid = torch.empty(E, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    ws_bytes = L.nonode_graph_workspace_bytes(E, n_nodes)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+    _lib.check(L.nonode_graph_build(_lib.ptr(r), _lib.ptr(c), r.element_size(), E, n_nodes, _lib.ptr(row_ptr),
+                                    _lib.ptr(col), _lib.ptr(eid), _lib.ptr(st.flag), _lib.ptr(ws), ws_bytes,
+                                    _lib.stream_of(row_ptr)))
+    if rows.is_cuda:   # (a host list was range-checked above: nothing pending for it)
+        st.unconfirmed.append(key)
+        st.csr_keys.add(key)
+    _csr[key] = (row_ptr, col, eid, rows, cols)
+    while len(_csr) > _CACHE:
+        _csr.popitem(last=False)
+    return row_ptr, col, eid

@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from . import graph as _graph
 from .graph import check_full_graph, finish
 
 
@@ -55,12 +56,19 @@ class SEGNO(nn.Module):
     Supported: SiLU, hidden_nf=64, in_edge_nf <= 4, tanh (coordinate MLP output through tanh,
     gcl.py:57-59), norm_diff (stored, unused in the reference's forward, gcl.py:32,63); single
     input (x [BN, 3]) or several (x [BN, I, 3] with in_steps, multiple_agg 'sum' / 'attn').
+
+    graph (keyword, not in the reference, like bug_compat): "full" (default) takes exactly the dataset's
+    fully connected, equal-size batch; "any" also takes every other edge list (inference only) on the
+    CSR graph kernels (csrc/nonode_graph.hip), while a list already known to be full keeps the fused path.
     """
 
     def __init__(self, in_node_nf, in_edge_nf, hidden_nf, device='cpu', act_fn=nn.SiLU(), n_layers=4,
                  coords_weight=1.0, recurrent=False, norm_diff=False, tanh=False, invariant=True,
-                 norm_vel=True, varDT=False, multiple_agg=None, bug_compat=False):
+                 norm_vel=True, varDT=False, multiple_agg=None, bug_compat=False, *, graph="full"):
         super().__init__()
+        if graph not in ("full", "any"):
+            raise ValueError(f'graph must be "full" or "any", got {graph!r}')
+        self.graph = graph
         unsupported = []
         if hidden_nf != 64:
             unsupported.append(f"hidden_nf={hidden_nf}")
@@ -169,7 +177,7 @@ class SEGNO(nn.Module):
         if self.bug_compat:
             # the live reference forward returns its inputs (and the embedded h)
             return x, self._embed(his), v
-        if self._tapes(his, x, v):
+        if self._tapes(his, x, v) and not self._general(edges, x.shape[0], True):
             if his.shape[-1] > 40:   # (nonode_embedding_* take up to 40 input features)
                 return self._step(self._embed(his), x, edges, v, edge_attr, int(T), tape=True)
             # the embedding and the T substeps as one autograd node (autograd.SEGNOTrain)
@@ -222,7 +230,8 @@ class SEGNO(nn.Module):
     def _step(self, h, x, edges, v, edge_attr, T, tape=None):
         """forward_step from an embedded h: on the autograd tape in training (tape: the caller's own
         decision, the single-input forms' _tapes), else the fused inference launch."""
-        if not (self._training() if tape is None else tape):
+        tape = self._training() if tape is None else tape
+        if not tape or self._general(edges, x.shape[0], tape):
             return self._run(None, h, x, edges, v, edge_attr, T)
         _lib.require_device(h)
         B, N = self._check_inputs(x, edges, v, edge_attr)
@@ -252,8 +261,48 @@ class SEGNO(nn.Module):
             out = out + x[..., k:k + 1] * w[:, k]
         return out
 
+    def _general(self, edges, n_nodes, tapes):
+        """Whether this call takes the general-graph path (graph="any" and an edge list not already
+        known to be the fully connected one). Inference only: refused before any device work otherwise."""
+        if self.graph != "any" or _graph.known_full(edges, n_nodes) is not None:
+            return False
+        if tapes:
+            raise NotImplementedError("general graphs: inference only")
+        _graph.check_host_range(edges, n_nodes)
+        return True
+
+    @torch.no_grad()
+    def _run_graph(self, his, h_in, x, edges, v, edge_attr, T):
+        """model.py:73,95-102 on any edge list (graph="any"): nonode_segno_forward_step_graph over the
+        CSR of graph.csr; edge_attr [E, in_edge_nf]."""
+        _lib.require_device(his, h_in, x, v, edge_attr, self.embedding.weight)
+        n = x.shape[0]
+        E = _graph._split(edges)[0].numel()
+        if edge_attr.shape != (E, self.in_edge_nf):
+            raise ValueError(f"edge_attr must be [{E}, {self.in_edge_nf}]")
+        f32 = lambda t: t.detach().to(torch.float32).contiguous() if t is not None else None  # noqa: E731
+        x, v, ea, his, h_in = f32(x), f32(v), f32(edge_attr), f32(his), f32(h_in)
+        dev = x.device
+        row_ptr, col, eid = _graph.csr(edges, n, device=dev)
+        blob = self._packed()
+        x_out = torch.empty(n, 3, device=dev)
+        v_out = torch.empty(n, 3, device=dev)
+        h_out = torch.empty(n, self.hidden_nf, device=dev)
+        L = _lib.lib()
+        ws_bytes = L.nonode_segno_graph_workspace_bytes(n)
+        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev)
+        ew, eb = f32(self.embedding.weight), f32(self.embedding.bias)
+        _lib.check(L.nonode_segno_forward_step_graph(
+            n, E, T, self.in_node_nf, self.in_edge_nf, _lib.ptr(his), _lib.ptr(h_in), _lib.ptr(x), _lib.ptr(v),
+            _lib.ptr(ea), _lib.ptr(ew), _lib.ptr(eb), _lib.ptr(blob), _lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(eid),
+            float(self.coords_weight), int(bool(self.recurrent)), _lib.ptr(x_out), _lib.ptr(v_out), _lib.ptr(h_out),
+            _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
+        return finish((x_out, h_out, v_out))
+
     @torch.no_grad()
     def _run(self, his, h_in, x, edges, v, edge_attr, T):
+        if self._general(edges, x.shape[0], False):
+            return self._run_graph(his, h_in, x, edges, v, edge_attr, T)
         _lib.require_device(x, v, edge_attr, self.embedding.weight)
         BN = x.shape[0]
         B, N = check_full_graph(edges, BN)

@@ -1,0 +1,208 @@
+"""Timings of the general-graph path (EGNO graph="any", csrc/nonode_graph.hip) on the GPU. One JSON
+line per case on stdout (DESIGN.md section 3.7 quotes them; raw lines under profiles/graph/).
+
+python tools/bench_graph.py [--case price|knn|all] [--reps 7] [--iters 20]
+
+  price  the C2 graph (B = 512, N = 20, T = 10: 5120 fully connected graphs per layer launch) through
+         the fused layer entry (nonode_egnn_layer) and, passed as an edge list, through the general one
+         (nonode_egnn_layer_graph: projection + edge walk + node update). Per-layer time of each, the
+         two alternated `reps` times on the same box; the ratio is the price of generality.
+  knn    8 graphs x 1000 nodes, the 16 nearest neighbours of each node as its senders, T = 10, 4
+         layers: EGNO(graph="any") per forward against oracle/torch_ref.egno_forward (the reference's own
+         formulation: gathers, Linear, index_add) in fp32 on the same device, alternated likewise; and
+         the edge walk's share of the fp16x3 ceiling from the layer's time as an upper bound on the edge
+         walk's own (kernel times proper: rocprofv3 --kernel-trace --stats of this script, in a run of
+         its own).
+Times are device events around `iters` back-to-back calls after a warm-up; each case reports the median
+over the reps and the spread (min, max) beside it.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import no_node_comparison_amd as pkg  # noqa: E402
+from no_node_comparison_amd import _lib, graph  # noqa: E402
+from oracle import torch_ref as tr  # noqa: E402
+
+DEV = torch.device("cuda:0")
+FP16X3_PEAK_TFLOPS = 2500.0 / 3.0   # bench.py: dense fp16 MFMA peak / 3 (fp16x3 split products)
+MAC_PER_EDGE = 8448                 # bench.py: edge MLP + coordinate MLP of one edge
+MAC_PER_NODE = 24640
+
+
+def timed(fn, iters):
+    """ms per call: device events around `iters` back-to-back calls."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def alternate(arms, reps, iters):
+    """{name: [ms per rep]}: every arm warmed up, then the arms alternated `reps` times."""
+    for fn in arms.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    out = {k: [] for k in arms}
+    for _ in range(reps):
+        for k, fn in arms.items():
+            out[k].append(timed(fn, iters))
+    return out
+
+
+def stats(ms):
+    return {"median_ms": float(np.median(ms)), "min_ms": float(np.min(ms)), "max_ms": float(np.max(ms)), "reps": len(ms)}
+
+
+def synthetic(B, N, seed):
+    g = torch.Generator().manual_seed(seed)
+    sigma = (N / 5.0) ** (1.0 / 3.0)
+    loc = torch.randn(B, N, 3, generator=g) * sigma
+    vel = torch.randn(B, N, 3, generator=g)
+    vel = vel / vel.norm(dim=-1, keepdim=True) * 0.5
+    q = (torch.randint(0, 2, (B, N, 1), generator=g) * 2 - 1).float()
+    return loc.to(DEV), vel.to(DEV), q.to(DEV)
+
+
+def model(T, **kw):
+    torch.manual_seed(0)
+    return pkg.EGNO(n_layers=4, in_node_nf=2, in_edge_nf=2, hidden_nf=64, with_v=True, num_modes=2, num_timesteps=T,
+                    time_emb_dim=32, device=DEV, **kw).eval()
+
+
+def case_price(args):
+    B, N, T = 512, 20, 10
+    L, P = pkg.lib(), _lib.ptr
+    m = model(T)
+    blobs, _ = m._packed()
+    loc, vel, q = synthetic(B, N, 1)
+    rows, cols = graph.full_edges(B, N, DEV)
+    x1, v1 = loc.reshape(-1, 3), vel.reshape(-1, 3)
+    ef = torch.cat([(q.reshape(-1, 1)[rows] * q.reshape(-1, 1)[cols]), ((x1[rows] - x1[cols]) ** 2).sum(1, keepdim=True)],
+                   1).contiguous()
+    n, E = B * N, rows.numel()
+    torch.manual_seed(1)
+    h = (torch.randn(T * n, 64, device=DEV) * 0.5).contiguous()
+    x, v = x1.repeat(T, 1).contiguous(), v1.repeat(T, 1).contiguous()
+    ho, xo = torch.empty_like(h), torch.empty_like(x)
+    ho2, xo2 = torch.empty_like(h), torch.empty_like(x)
+    rp, cc, ee = graph.csr([rows.clone(), cols.clone()], n)
+    ws_bytes = L.nonode_egnn_layer_graph_workspace_bytes(T, n)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=DEV)
+    s = _lib.stream_of(h)
+
+    def fused():
+        _lib.check(L.nonode_egnn_layer(_lib.VARIANT_EGNO, T * B, N, 2, B, P(h), P(x), P(v), P(ef), P(blobs[0]), 0.0, 1.0, 0,
+                                       P(ho), P(xo), None, s))
+
+    def general():
+        _lib.check(L.nonode_egnn_layer_graph(_lib.VARIANT_EGNO, T, n, E, 2, 1, P(h), P(x), P(v), P(ef), P(blobs[0]), P(rp),
+                                             P(cc), P(ee), 0.0, 1.0, 0, P(ho2), P(xo2), None, P(ws), ws_bytes, s))
+
+    t = alternate({"fused": fused, "general": general}, args.reps, args.iters)
+    torch.cuda.synchronize()
+    err = float((ho - ho2).abs().max() / ho.abs().max())
+    f, g = stats(t["fused"]), stats(t["general"])
+    return {"case": "price", "shape": {"B": B, "N": N, "T": T, "edges_per_layer": T * E},
+            "fused_layer": f, "general_layer": g, "ratio_general_over_fused": g["median_ms"] / f["median_ms"],
+            "ratio_per_rep": [b / a for a, b in zip(t["fused"], t["general"])],
+            "h_maxnorm_rel_general_vs_fused": err, "iters": args.iters}
+
+
+def knn_graph(loc, k):
+    """rows (receivers), cols (their k nearest neighbours) of B graphs, node ids offset per graph."""
+    B, N, _ = loc.shape
+    d = torch.cdist(loc, loc)
+    d.diagonal(dim1=1, dim2=2).fill_(float("inf"))
+    nb = d.topk(k, dim=2, largest=False).indices                     # [B, N, k]
+    off = (torch.arange(B, device=loc.device) * N)[:, None, None]
+    rows = (torch.arange(N, device=loc.device)[None, :, None] + off).expand(B, N, k).reshape(-1)
+    return rows.contiguous(), (nb + off).reshape(-1).contiguous()
+
+
+def case_knn(args):
+    B, N, T, K = 8, 1000, 10, 16
+    m = model(T, graph="any")
+    loc, vel, q = synthetic(B, N, 2)
+    rows, cols = knn_graph(loc, K)
+    x, v = loc.reshape(-1, 3).contiguous(), vel.reshape(-1, 3).contiguous()
+    qq = q.reshape(-1, 1)
+    ef = torch.cat([qq[rows] * qq[cols], ((x[rows] - x[cols]) ** 2).sum(1, keepdim=True)], 1).contiguous()
+    h = torch.cat([v.norm(dim=1, keepdim=True), qq], 1).contiguous()
+    lm = loc.mean(1, keepdim=True).repeat(1, N, 1).reshape(-1, 3).contiguous()
+    t_out = torch.arange(1, T + 1, device=DEV).repeat(B, 1)
+    n, E = B * N, rows.numel()
+    p32 = {k_: t.detach().float() for k_, t in m.state_dict().items()}
+    tf = t_out.float()
+
+    def ours():
+        with torch.no_grad():
+            return m(x, h, [rows, cols], ef, v=v, loc_mean=lm, timesteps_out=t_out)
+
+    def ref():
+        with torch.no_grad(), torch.device(DEV):   # (torch_ref's factory calls take the default device)
+            return tr.egno_forward(p32, x, h, rows, cols, ef, v, lm, tf, T=T)
+
+    t = alternate({"general": ours, "torch_ref": ref}, args.reps, max(args.iters // 4, 3))
+    a, b = ours(), ref()
+    torch.cuda.synchronize()
+    err = [float((u - w).abs().max() / w.abs().max()) for u, w in zip(a, b)]
+    # one layer through the C entry: the three launches' time bounds the edge walk's from above
+    L, P = pkg.lib(), _lib.ptr
+    blobs, _ = m._packed()
+    rp, cc, ee = graph.csr([rows, cols], n)
+    torch.manual_seed(3)
+    hh = (torch.randn(T * n, 64, device=DEV) * 0.5).contiguous()
+    xx, vv = x.repeat(T, 1).contiguous(), v.repeat(T, 1).contiguous()
+    ho, xo = torch.empty_like(hh), torch.empty_like(xx)
+    ws_bytes = L.nonode_egnn_layer_graph_workspace_bytes(T, n)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=DEV)
+    s = _lib.stream_of(hh)
+
+    def layer():
+        _lib.check(L.nonode_egnn_layer_graph(_lib.VARIANT_EGNO, T, n, E, 2, 1, P(hh), P(xx), P(vv), P(ef), P(blobs[0]),
+                                             P(rp), P(cc), P(ee), 0.0, 1.0, 0, P(ho), P(xo), None, P(ws), ws_bytes, s))
+
+    tl = stats(alternate({"layer": layer}, args.reps, args.iters)["layer"])
+    flop_edges = 2.0 * T * E * MAC_PER_EDGE
+    flop_layer = flop_edges + 2.0 * T * n * MAC_PER_NODE
+    g, r = stats(t["general"]), stats(t["torch_ref"])
+    return {"case": "knn", "shape": {"graphs": B, "nodes_per_graph": N, "k": K, "T": T, "layers": 4, "E": E},
+            "general_forward": g, "torch_ref_fp32_forward": r, "speedup_over_torch_ref": r["median_ms"] / g["median_ms"],
+            "speedup_per_rep": [b_ / a_ for a_, b_ in zip(t["general"], t["torch_ref"])],
+            "maxnorm_rel_vs_torch_ref_xvh": err,
+            "layer_three_launches": tl, "layer_algorithmic_gflop": flop_layer / 1e9,
+            "layer_frac_of_fp16x3_peak": flop_layer / (tl["median_ms"] * 1e-3) / 1e12 / FP16X3_PEAK_TFLOPS,
+            "edge_walk_algorithmic_gflop": flop_edges / 1e9,
+            "edge_walk_frac_of_fp16x3_peak_lower_bound": flop_edges / (tl["median_ms"] * 1e-3) / 1e12 / FP16X3_PEAK_TFLOPS,
+            "peak_basis": "dense fp16 MFMA peak / 3 (fp16x3 split products), as bench.py --full prices the fused layer"}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--case", default="all", choices=["price", "knn", "all"])
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=20)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/bench_graph.py measures on the GPU: no ROCm device found")
+    for name, fn in (("price", case_price), ("knn", case_knn)):
+        if args.case in (name, "all"):
+            res = fn(args)
+            res["device"] = torch.cuda.get_device_name(0)
+            print(json.dumps(res), flush=True)
+    graph.sync_checks()
+
+
+if __name__ == "__main__":
+    main()
