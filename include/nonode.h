@@ -17,7 +17,8 @@
  *                   (b, i, j != i)  (EGNO/simulation/dataset_simple.py:64-71,101-111)
  *   graphs          fully connected, equal size N, no self loops; row = receiver i,
  *                   col = sender j (basic.py:168-186, gcl.py:111-119). The *_graph entries at the
- *                   end take any edge list instead, as a CSR by receiver (inference).
+ *                   end take any edge list instead, as a CSR by receiver (inference; EGNO training:
+ *                   nonode_egnn_layer_graph_bwd).
  */
 #ifndef NONODE_H_
 #define NONODE_H_
@@ -538,7 +539,7 @@ int nonode_check_full_edges(const void* rows, const void* cols, int idx_bytes, l
 int nonode_poison_if_flagged(const int* flag, int n_bufs, float* const* bufs, const long long* counts, void* stream);
 
 
-/* ---- arbitrary edge lists: CSR graph kernels (inference) ---- */
+/* ---- arbitrary edge lists: CSR graph kernels (inference, and the EGNO layer's reverse) ---- */
 
 /*
  * The `edges` argument of EGNN_Layer.forward (basic.py:167-186, aggregate basic.py:6-31) and
@@ -572,6 +573,51 @@ int nonode_egnn_layer_graph(int variant, int n_frames, int n_nodes, long long E,
                             const int* row_ptr, const int* col, const int* eid, float dt, float coords_weight,
                             int recurrent, float* h_out, float* x_out, float* v_out, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/*
+ * ---- training on an explicit edge list (EGNO graph="trainable"; csrc/nonode_graph_train.hip) ----
+ *
+ * The training forward of the graph layer IS nonode_egnn_layer_graph: its workspace is the state the
+ * reverse pass reads, so a caller that trains keeps the workspace alive until the backward. Layout
+ * (floats, n = n_frames * n_nodes): P [n][64] | Q [n][64] (the first edge Linear's receiver / sender
+ * projections, InvariantScalarNet basic.py:107-123, in the packed blob's log2-domain scale), M [n][64]
+ * (message sums, aggregate basic.py:6-31, same scale), F [n][4] = (force sum x3, in-degree).
+ *
+ * nonode_graph_edge_mask: valid[e] = 1 for every edge nonode_graph_build kept (row_ptr, eid of the CSR
+ * by receiver), 0 for the ones it dropped (an index out of range).
+ *
+ * nonode_egnn_layer_graph_bwd, variant EGNO: the reverse of EGNN_Layer.forward (basic.py:167-186:
+ * edge message basic.py:170 / 107-144, coord_net and the aggregate basic.py:171-177 / 6-31, node_v_net
+ * and the x update basic.py:178-181, node_net basic.py:182-185) for frames [f0, f1) of the n_frames the
+ * forward ran. Inputs: the layer's inputs h, x, v, edge_fea, its forward blob, the backward blob of
+ * nonode_pack_layer_bwd, the forward's state, the CSR by receiver (row_ptr, col, eid), the CSR by sender
+ * (srow_ptr, seid: nonode_graph_build with rows and cols swapped), valid (nonode_graph_edge_mask, or
+ * NULL when no edge was dropped) and the gradients g_x, g_v, g_h of x_out, v_out, h_out (full
+ * [n_frames * n_nodes] arrays; NULL = 0). Writes rows f0 * n_nodes .. f1 * n_nodes of g_h_in [.][64],
+ * g_x_in, g_v_in [.][3], and the operands of the weight gradients for those frames, rows relative to f0:
+ *   node_ops [(f1-f0) n_nodes][520]: 0 dL/dh part | 64 dL/dM | 128 gz (node_net hidden pre-activation
+ *     gradient) | 192 z (its activation) | 256 gt | 320 t (node_v_net likewise) | 384 GA = sum over
+ *     incoming edges of gz1 | 448 GB = sum over outgoing edges of gz1 | 512 dL/dF x3, gphi | 516 the
+ *     receiver's share of dL/dx x3, 0
+ *   edge_ops [(f1-f0)][E][400], row = the edge's ORIGINAL index: 0 gz1 | 64 gz2 | 128 a | 192 (1, s, e_0 ..
+ *     e_3, 0, 0: the ones column, the radial input, the edge's features) | 200 gz3 | 264 gc, dL/dr x3 |
+ *     268 m | 332 (1, 0, 0, 0) | 336 c1 (gz*: the edge MLP's and coord_net's pre-activation gradients; a, m,
+ *     c1: their true-scale activations). Rows of dropped edges are zero when valid is given.
+ * Every weight gradient is a sum over nodes or edges of outer products of these rows (the caller's GEMMs,
+ * accumulated over frame groups; the edge-level ones are [gz1 | gz2]^T [a | 1, s, e] and
+ * [gz3 | gc]^T [m | 1 | c1]): the frame range bounds edge_ops. No float atomics: per-receiver and
+ * per-sender sums are added in CSR order, so g_*_in are bitwise reproducible and, for a list without
+ * duplicate edges, independent of the list's order. Asynchronous; allocates nothing.
+ */
+int nonode_graph_edge_mask(const int* row_ptr, const int* eid, int n_nodes, long long E, int* valid, void* stream);
+size_t nonode_egnn_layer_graph_bwd_node_floats(int n_frames, int n_nodes);
+size_t nonode_egnn_layer_graph_bwd_edge_floats(int n_frames, long long E);
+int nonode_egnn_layer_graph_bwd(int variant, int n_frames, int n_nodes, long long E, int n_edge_feat, int ef_frames,
+                                int f0, int f1, const float* h, const float* x, const float* v, const float* edge_fea,
+                                const float* blob, const float* bblob, const float* state, const int* row_ptr,
+                                const int* col, const int* eid, const int* srow_ptr, const int* seid, const int* valid,
+                                const float* g_x, const float* g_v, const float* g_h, float* node_ops, float* edge_ops,
+                                float* g_h_in, float* g_x_in, float* g_v_in, void* stream);
 
 /*
  * EGNO.forward (EGNO/model/egno.py:37-111) on an explicit edge list: the arguments of

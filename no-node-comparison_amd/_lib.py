@@ -40,6 +40,8 @@ SYMBOLS = (
     "nonode_graph_workspace_bytes", "nonode_graph_build", "nonode_egnn_layer_graph_workspace_bytes",
     "nonode_egnn_layer_graph", "nonode_egno_graph_workspace_bytes", "nonode_egno_forward_graph",
     "nonode_segno_graph_workspace_bytes", "nonode_segno_forward_step_graph",
+    "nonode_graph_edge_mask", "nonode_egnn_layer_graph_bwd_node_floats", "nonode_egnn_layer_graph_bwd_edge_floats",
+    "nonode_egnn_layer_graph_bwd",
 )
 
 VARIANT_EGNO = 0
@@ -245,6 +247,12 @@ def lib():
     L.nonode_segno_graph_workspace_bytes.restype = _sz
     L.nonode_segno_forward_step_graph.argtypes = ([_i, _ll, _i, _i, _i] + [_vp] * 11 + [_f, _i] + [_vp] * 4
                                                   + [_sz, _vp])
+    L.nonode_graph_edge_mask.argtypes = [_vp, _vp, _i, _ll, _vp, _vp]
+    L.nonode_egnn_layer_graph_bwd_node_floats.argtypes = [_i, _i]
+    L.nonode_egnn_layer_graph_bwd_node_floats.restype = _sz
+    L.nonode_egnn_layer_graph_bwd_edge_floats.argtypes = [_i, _ll]
+    L.nonode_egnn_layer_graph_bwd_edge_floats.restype = _sz
+    L.nonode_egnn_layer_graph_bwd.argtypes = [_i] * 3 + [_ll] + [_i] * 4 + [_vp] * 22
     L.nonode_profile_begin.argtypes = [_i]
     L.nonode_profile_end.argtypes = [ctypes.POINTER(_f), ctypes.POINTER(_i), _i]
     for s in SYMBOLS:

@@ -410,12 +410,12 @@ class FlatLayerTrain(torch.autograd.Function):
                                                                              g_txw.to(params[17].dtype))
 
 
-def egno_flat_train(model, x, h, edge_fea, v, loc_mean, t_out, B, N):
-    """EGNO(flat=True).forward in training (egno.py:37-111, num_inputs == 1): the time embedding and the
-    embedding Linear as torch ops, then one FlatLayerTrain node per layer."""
+def _embed_frames(model, x, h, v, loc_mean, t_out, BN):
+    """The head of EGNO.forward (egno.py:37-96, num_inputs == 1) as torch ops on the tape: the time
+    embedding, the embedding Linear and the T-fold replication. Returns (h [T*BN, 64], x, v [T*BN, 3],
+    loc_mean as f32 or None without time convolutions)."""
     import math
     T = model.num_timesteps
-    BN = B * N
     dim, half = model.time_emb_dim, model.time_emb_dim // 2
     # get_timestep_embedding (layer_no.py:8-17)
     freqs = torch.exp(torch.arange(half, dtype=torch.float32, device=x.device) * -(math.log(10000) / (half - 1)))
@@ -428,9 +428,201 @@ def egno_flat_train(model, x, h, edge_fea, v, loc_mean, t_out, B, N):
     hh = model.embedding(torch.cat([h.float()[None].expand(T, -1, -1), temb], -1).reshape(T * BN, -1))
     xx, vv = x.float().repeat(T, 1), v.float().repeat(T, 1)                             # egno.py:89-96
     lm = loc_mean.float() if model.use_time_conv else None
+    return hh, xx, vv, lm
+
+
+def egno_flat_train(model, x, h, edge_fea, v, loc_mean, t_out, B, N):
+    """EGNO(flat=True).forward in training (egno.py:37-111, num_inputs == 1): the time embedding and the
+    embedding Linear as torch ops, then one FlatLayerTrain node per layer."""
+    hh, xx, vv, lm = _embed_frames(model, x, h, v, loc_mean, t_out, B * N)
     for i in range(model.n_layers):
         params = _flat_layer_params(model, i)
         if model.use_time_conv:
             params += [model.time_conv_modules[i].t_conv.weights1, model.time_conv_x_modules[i].t_conv.weights1]
         hh, xx, vv = FlatLayerTrain.apply(model, i, B, N, hh, xx, vv, lm, edge_fea, *params)
+    return xx, vv, hh
+
+
+# ---- EGNO(graph="trainable") training on any edge list (csrc/nonode_graph_train.hip) ------------------
+# One autograd node per layer, as FlatLayerTrain: TimeConv + TimeConv_x, then the graph layer
+# (nonode_egnn_layer_graph, whose workspace is the saved state) and its reverse
+# (nonode_egnn_layer_graph_bwd: HIP kernels for everything per node and per edge). The weight gradients
+# are sums over nodes or edges of outer products of the operand rows the reverse writes: GEMMs on the
+# device, accumulated over groups of frames.
+#
+# GRAPH_OPS_CAP_BYTES bounds the per-edge operand buffer of one group (400 floats per edge and frame):
+# the reverse runs frames [f0, f1) per call with (f1 - f0) * E * 1600 bytes under the cap (at least one
+# frame). 1 GiB: a group then still holds several hundred thousand rows, enough for the GEMMs to run at
+# their large-K rate (a k-NN graph of 8 x 1000 nodes with 16 neighbours is 5 frames per group), while the
+# transient stays a fraction of a percent of the device's HBM however many frames or edges a model has.
+# (A model attribute `graph_ops_cap_bytes`, if set, takes its place for that model.)
+GRAPH_OPS_CAP_BYTES = 1 << 30
+_GN = dict(GHP=0, GM=64, GZ=128, Z=192, GT=256, T=320, GA=384, GB=448, GF=512, GX=516, STRIDE=520)
+_GE = dict(GZ1=0, GZ2=64, A=128, X8=192, GZ3=200, GC=264, M=268, ONE=332, C1=336, STRIDE=400)
+_NEG_LN2 = -0.6931471805599453   # the forward's state keeps M in the packed blob's log2-domain scale
+
+
+def _tn(X, Y, split=256):
+    """X^T Y of tall operands X [rows, a], Y [rows, b] (column slices of an operand buffer). A 64 x 64 result
+    alone gives the GEMM a handful of workgroups for a million rows, so the rows are cut into `split` equal
+    chunks, multiplied as one batch and added in chunk order (a fixed order: deterministic)."""
+    rows = X.shape[0]
+    c = rows // split
+    if c < 64:
+        return X.t() @ Y
+    main = c * split
+    out = torch.bmm(X[:main].unflatten(0, (split, c)).transpose(1, 2), Y[:main].unflatten(0, (split, c))).sum(0)
+    return out if main == rows else out + X[main:].t() @ Y[main:]
+
+
+def graph_frame_groups(n_frames, E, cap_bytes=None):
+    """[(f0, f1), ...]: the frame groups of one layer's reverse under the operand cap."""
+    cap = GRAPH_OPS_CAP_BYTES if cap_bytes is None else cap_bytes
+    per = max(1, int(cap // max(1, E * _GE["STRIDE"] * 4)))
+    return [(f0, min(f0 + per, n_frames)) for f0 in range(0, n_frames, per)]
+
+
+def graph_layer_reverse(n_frames, n, E, ne, ef_frames, h, x, v, ef, blob, bblob, state, csr, scsr, gx, gv, gh,
+                        cap_bytes=None, want_w=True):
+    """nonode_egnn_layer_graph_bwd over the frame groups plus the weight-gradient GEMMs. h [n_frames*n, 64],
+    x, v [.., 3], ef [ef_frames * E, ne] (f32, contiguous), state: the workspace nonode_egnn_layer_graph
+    filled, csr = (row_ptr, col, eid), scsr = (srow_ptr, seid, valid) of graph.csr / graph.csr_by_sender,
+    gx, gv, gh: gradients of the layer's outputs (None = 0). Returns (g_h_in, g_x_in, g_v_in, grads) with
+    grads the 16 parameter gradients in nonode_layer_weights order (edge, coord, node_v, node MLP; the first
+    Linear's columns [s, h_i, h_j, e]; None with want_w=False, a frozen model's input gradients)."""
+    L = _lib.lib()
+    dev = h.device
+    nt = n_frames * n
+    row_ptr, col, eid = csr
+    srow_ptr, seid, valid = scsr
+    g_h, g_x, g_v = torch.empty(nt, 64, device=dev), torch.empty(nt, 3, device=dev), torch.empty(nt, 3, device=dev)
+    M = state[2 * nt * 64:3 * nt * 64].view(nt, 64)
+    ef3 = ef.reshape(ef_frames, E, ne) if ne else None
+    s = _lib.stream_of(h)
+    N_, E_ = _GN, _GE
+    total = None
+    for f0, f1 in graph_frame_groups(n_frames, E, cap_bytes):
+        nf = f1 - f0
+        nops = torch.empty(nf * n, N_["STRIDE"], device=dev)
+        eops = torch.empty(nf * E, E_["STRIDE"], device=dev)
+        _lib.check(L.nonode_egnn_layer_graph_bwd(
+            _lib.VARIANT_EGNO, n_frames, n, E, ne, ef_frames, f0, f1, _lib.ptr(h), _lib.ptr(x), _lib.ptr(v),
+            _lib.ptr(ef) if ne else None, _lib.ptr(blob), _lib.ptr(bblob), _lib.ptr(state), _lib.ptr(row_ptr),
+            _lib.ptr(col), _lib.ptr(eid), _lib.ptr(srow_ptr), _lib.ptr(seid), _lib.ptr(valid), _lib.ptr(gx), _lib.ptr(gv),
+            _lib.ptr(gh), _lib.ptr(nops), _lib.ptr(eops) if E else None, _lib.ptr(g_h), _lib.ptr(g_x), _lib.ptr(g_v), s))
+        if not want_w:
+            continue
+        nc = lambda k, w=64: nops[:, N_[k]:N_[k] + w]  # noqa: E731
+        hs = h[f0 * n:f1 * n]
+        hM = torch.cat([hs, M[f0 * n:f1 * n] * _NEG_LN2], 1)
+        gz, z_, gt = nc("GZ"), nc("Z"), nc("GT")
+        gphi = nops[:, N_["GF"] + 3:N_["GF"] + 4]
+        # node level: [GA | GB]^T h, gt^T h, gz^T [h | M], gho^T z, gphi^T t
+        e1h = _tn(nc("GA", 128), hs)
+        if E:
+            # edge level: [gz1 | gz2]^T [a | 1, s, e] and [gz3 | gc]^T [m | 1 | c1]
+            e1 = _tn(eops[:, E_["GZ1"]:E_["GZ1"] + 128], eops[:, E_["A"]:E_["A"] + 72])
+            e2 = _tn(eops[:, E_["GZ3"]:E_["GZ3"] + 65], eops[:, E_["M"]:E_["M"] + 132])
+        else:
+            e1, e2 = torch.zeros(128, 72, device=dev), torch.zeros(65, 132, device=dev)
+        w1 = [e1[:64, 65:66], e1h[:64], e1h[64:]] + ([e1[:64, 66:66 + ne]] if ne else [])
+        if gh is not None:
+            gho = gh[f0 * n:f1 * n]
+            dn2, dbn2 = _tn(gho, z_), gho.sum(0)
+        else:
+            dn2, dbn2 = torch.zeros(64, 64, device=dev), torch.zeros(64, device=dev)
+        grads = [torch.cat(w1, 1), e1[:64, 64], e1[64:, :64], e1[64:, 64],            # edge MLP
+                 e2[:64, :64], e2[:64, 64], e2[64:, 68:132], e2[64, 64:65],            # coord MLP
+                 _tn(gt, hs), gt.sum(0), _tn(gphi, nc("T")), gphi.sum(0),              # node_v MLP
+                 _tn(gz, hM), gz.sum(0), dn2, dbn2]                                    # node MLP
+        total = grads if total is None else [a + b for a, b in zip(total, grads)]
+    return g_h, g_x, g_v, total
+
+
+class GraphLayerTrain(torch.autograd.Function):
+    """TimeConv (+ TimeConv_x) of layer i, then its EGNN layer on an explicit edge list (egno.py:99-111
+    with any `edges`)."""
+
+    @staticmethod
+    def forward(ctx, model, i, n, E, graph, h, x, v, loc_mean, ef, *params):
+        L = _lib.lib()
+        T = model.num_timesteps
+        dev = h.device
+        nt = T * n
+        h, x, v, ef = _f32(h), _f32(x), _f32(v), _f32(ef)
+        blobs, tblobs = model._packed()
+        s = _lib.stream_of(h)
+        if model.use_time_conv:
+            lm = _f32(loc_mean)
+            tcx = _f32(model.time_conv_x_modules[i].t_conv.weights1)
+            ht, xt, vt = torch.empty(nt, 64, device=dev), torch.empty(nt, 3, device=dev), torch.empty(nt, 3, device=dev)
+            _lib.check(L.nonode_egno_tconv(n, T, model.num_modes, _lib.ptr(h), _lib.ptr(x), _lib.ptr(v), _lib.ptr(lm),
+                                           _lib.ptr(tblobs[i]), _lib.ptr(tcx), _lib.ptr(ht), _lib.ptr(xt), _lib.ptr(vt),
+                                           s))
+        else:
+            lm, ht, xt, vt = None, h, x, v
+        row_ptr, col, eid = graph[0]
+        st_bytes = L.nonode_egnn_layer_graph_workspace_bytes(T, n)
+        state = torch.empty((st_bytes + 3) // 4, device=dev)   # the layer's workspace is the saved state
+        h_out, x_out = torch.empty(nt, 64, device=dev), torch.empty(nt, 3, device=dev)
+        _lib.check(L.nonode_egnn_layer_graph(
+            _lib.VARIANT_EGNO, T, n, E, model.in_edge_nf, 1, _lib.ptr(ht), _lib.ptr(xt), _lib.ptr(vt), _lib.ptr(ef),
+            _lib.ptr(blobs[i]), _lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(eid), 0.0, 1.0, 0, _lib.ptr(h_out),
+            _lib.ptr(x_out), None, _lib.ptr(state), st_bytes, s))
+        ctx.set_materialize_grads(False)
+        ctx.model, ctx.i, ctx.n, ctx.E, ctx.graph = model, i, n, E, graph
+        ctx.keep = (h, x, v, lm, ef, ht, xt, vt, state)
+        ctx.save_for_backward(*params)
+        return h_out, x_out, vt.clone() if vt is v else vt
+
+    @staticmethod
+    def backward(ctx, gh, gx, gv):
+        model, i, n, E = ctx.model, ctx.i, ctx.n, ctx.E
+        params = ctx.saved_tensors   # raises if a parameter changed in place since the forward
+        h, x, v, lm, ef, ht, xt, vt, state = ctx.keep
+        ctx.keep = None
+        L = _lib.lib()
+        T = model.num_timesteps
+        dev = h.device
+        gh, gx, gv = (_f32(g) if g is not None else None for g in (gh, gx, gv))
+        blobs, tblobs = model._packed()
+        bb = model._packed_bwd()
+        ght, gxt, gvt, grads = graph_layer_reverse(T, n, E, model.in_edge_nf, 1, ht, xt, vt, ef, blobs[i], bb[i], state,
+                                                   ctx.graph[0], ctx.graph[1], gx, gv, gh,
+                                                   getattr(model, "graph_ops_cap_bytes", None),
+                                                   want_w=any(ctx.needs_input_grad[10:26]))
+        grads = [g.reshape(p.shape).to(p.dtype) for g, p in zip(grads, params[:16])] if grads else [None] * 16
+        if not model.use_time_conv:
+            return (None,) * 5 + (ght, gxt, gvt, None, None) + tuple(grads)
+        g_h, g_x, g_v = torch.empty_like(h), torch.empty_like(x), torch.empty_like(v)
+        tw, txw = _f32(params[16]), _f32(params[17])      # kept alive over the call
+        g_tw, g_txw = torch.empty_like(tw), torch.empty_like(txw)
+        ws_bytes = L.nonode_egno_tconv_bwd_workspace_bytes(n, T, model.num_modes)
+        ws = torch.empty((ws_bytes + 3) // 4, device=dev)
+        _lib.check(L.nonode_egno_tconv_bwd(n, T, model.num_modes, _lib.ptr(h), _lib.ptr(x), _lib.ptr(v), _lib.ptr(lm),
+                                           _lib.ptr(tblobs[i]), _lib.ptr(tw), _lib.ptr(txw), _lib.ptr(ght),
+                                           _lib.ptr(gxt), _lib.ptr(gvt), _lib.ptr(g_h), _lib.ptr(g_x), _lib.ptr(g_v),
+                                           _lib.ptr(g_tw), _lib.ptr(g_txw), _lib.ptr(ws), ws_bytes, _lib.stream_of(h)))
+        sink = getattr(model, "_train_bwd_sink", None)
+        if sink is not None:   # tests: the workspace head holds the LeakyReLU decisions the reverse used
+            sink.append((i, ws))
+        g_lm = _tconvx_lm_grad(gxt, gvt, txw, T, model.num_modes) if ctx.needs_input_grad[8] else None
+        return (None,) * 5 + (g_h, g_x, g_v, g_lm, None) + tuple(grads) + (g_tw.to(params[16].dtype),
+                                                                             g_txw.to(params[17].dtype))
+
+
+def egno_graph_train(model, x, h, edge_index, edge_fea, v, loc_mean, t_out):
+    """EGNO(graph="trainable").forward on the tape (egno.py:37-111, num_inputs == 1, any edge list): the
+    time embedding and the embedding Linear as torch ops, then one GraphLayerTrain node per layer."""
+    from . import graph as _graph
+    n = h.shape[0]
+    E = _graph._split(edge_index)[0].numel()
+    csr = _graph.csr(edge_index, n, device=x.device)
+    scsr = _graph.csr_by_sender(edge_index, n, device=x.device)
+    hh, xx, vv, lm = _embed_frames(model, x, h, v, loc_mean, t_out, n)
+    for i in range(model.n_layers):
+        params = _flat_layer_params(model, i)
+        if model.use_time_conv:
+            params += [model.time_conv_modules[i].t_conv.weights1, model.time_conv_x_modules[i].t_conv.weights1]
+        hh, xx, vv = GraphLayerTrain.apply(model, i, n, E, (csr, scsr), hh, xx, vv, lm, edge_fea, *params)
     return xx, vv, hh

@@ -92,15 +92,17 @@ class EGNO(nn.Module):
     graph (keyword, not in the reference): "full" (default) takes exactly the dataset's fully connected,
     equal-size batch, as the fused kernels index it; "any" also takes every other edge list (inference
     only, not with flat=True) on the CSR graph kernels (csrc/nonode_graph.hip), while a list already
-    known to be the full one keeps the fused path.
+    known to be the full one keeps the fused path; "trainable" is "any" whose taped forward (training, or an
+    input among x, h, v, loc_mean that requires grad) also runs on every edge list: one autograd node per layer
+    (autograd.GraphLayerTrain, csrc/nonode_graph_train.hip), num_inputs=1, not with flat=True.
     """
 
     def __init__(self, n_layers, in_node_nf, in_edge_nf, hidden_nf, activation=nn.SiLU(), device='cpu',
                  with_v=False, flat=False, norm=False, use_time_conv=True, num_modes=2, num_timesteps=8,
                  time_emb_dim=32, num_inputs=1, varDT=False, fix_out_size=False, *, graph="full"):
         super().__init__()
-        if graph not in ("full", "any"):
-            raise ValueError(f'graph must be "full" or "any", got {graph!r}')
+        if graph not in ("full", "any", "trainable"):
+            raise ValueError(f'graph must be "full", "any" or "trainable", got {graph!r}')
         self.graph = graph
         unsupported = []
         if num_inputs < 1:
@@ -273,15 +275,23 @@ class EGNO(nn.Module):
         if v is None or (loc_mean is None and self.use_time_conv):
             raise ValueError("EGNO.forward needs v and loc_mean (the time convolution stacks "
                              "x - loc_mean with v, egno.py:103-105)")
+        tapes = self._tapes(x, h, v, loc_mean)
+        if self.graph == "trainable":   # refused before the edge_fea check and before any device work
+            if self.flat:
+                raise NotImplementedError('EGNO(graph="trainable") does not run with flat=True')
+            if tapes and self.num_inputs > 1 and _graph.known_full(edge_index, h.shape[-2]) is None:
+                raise NotImplementedError('EGNO(graph="trainable") trains the single-input model (num_inputs=1) '
+                                          "on general graphs")
         if torch.is_grad_enabled() and edge_fea is not None and edge_fea.requires_grad:
             raise NotImplementedError(
                 "EGNO.forward has no gradient for edge_fea: the reference's training and rollout loops detach "
                 "the edge features (main_simulation_simple_no.py:327,338) and the per-edge input gradient is "
                 "not built; pass edge_fea.detach()")
-        tapes = self._tapes(x, h, v, loc_mean)
         if self.flat and tapes and self.num_inputs > 1:
             raise NotImplementedError("EGNO(flat=True) training runs the single-input model (num_inputs=1)")
-        if self._general(edge_index, h.shape[-2], tapes):
+        if self._general(edge_index, h.shape[-2], tapes, (x, h, v, loc_mean, edge_fea)):
+            if tapes:
+                return self._forward_graph_train(x, h, edge_index, edge_fea, v, loc_mean, timesteps_out)
             return self._forward_graph(x, h, edge_index, edge_fea, v, loc_mean, timesteps_in, timesteps_out)
         if self.num_inputs > 1:
             return self._forward_multi(x, h, edge_index, edge_fea, v, loc_mean, timesteps_in, timesteps_out)
@@ -306,11 +316,17 @@ class EGNO(nn.Module):
             return finish(egno_forward_train(self, x, h, edge_fea, v, loc_mean, timesteps_out, B, N))
         return finish(self._forward_kernels(x, h, edge_fea, v, loc_mean, timesteps_out, B, N))
 
-    def _general(self, edge_index, n_nodes, tapes):
-        """Whether this forward takes the general-graph path (graph="any" and an edge list not already
-        known to be the fully connected one). Inference only: refused before any device work otherwise."""
-        if self.graph != "any" or _graph.known_full(edge_index, n_nodes) is not None:
+    def _general(self, edge_index, n_nodes, tapes, inputs=()):
+        """Whether this forward takes the general-graph path (graph="any" / "trainable" and an edge list not
+        already known to be the fully connected one). graph="any" is inference only: refused before any
+        device work otherwise; graph="trainable" also takes a taped forward (forward() has refused flat=True
+        and multi-input training by now)."""
+        if self.graph == "full" or _graph.known_full(edge_index, n_nodes) is not None:
             return False
+        if self.graph == "trainable":
+            _lib.require_device(*inputs, self.embedding.weight)
+            _graph.check_host_range(edge_index, n_nodes)
+            return True
         if tapes:
             raise NotImplementedError("general graphs: inference only")
         if self.flat:
@@ -371,6 +387,23 @@ class EGNO(nn.Module):
             _lib.ptr(ew), _lib.ptr(eb), blob_p, tcw_p, tcx_p, _lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(eid),
             _lib.ptr(x_out), _lib.ptr(v_out), _lib.ptr(h_out), _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
         return finish((x_out, v_out, h_out))
+
+    def _forward_graph_train(self, x, h, edge_index, edge_fea, v, loc_mean, timesteps_out):
+        """egno.py:37-111 on any edge list, on the autograd tape (graph="trainable", num_inputs == 1):
+        autograd.egno_graph_train. Shapes as _forward_graph's single-input form."""
+        T = self.num_timesteps
+        n = h.shape[-2]
+        E = _graph._split(edge_index)[0].numel()
+        if timesteps_out is None:
+            timesteps_out = torch.arange(T, device=x.device).unsqueeze(0)
+        if timesteps_out.dim() != 2 or timesteps_out.shape[1] != T:
+            raise ValueError(f"timesteps_out must be [B, {T}], got {tuple(timesteps_out.shape)}")
+        if n % timesteps_out.shape[0]:
+            raise ValueError("number of nodes must be a multiple of timesteps_out.shape[0] (egno.py:66)")
+        if edge_fea.shape != (E, self.in_edge_nf):
+            raise ValueError(f"edge_fea must be [{E}, {self.in_edge_nf}], got {tuple(edge_fea.shape)}")
+        from .autograd import egno_graph_train
+        return finish(egno_graph_train(self, x, h, edge_index, edge_fea, v, loc_mean, timesteps_out))
 
     def _trains(self):
         """Training forward: train mode, gradients enabled and a parameter that requires grad."""

@@ -22,6 +22,8 @@ by receiver (``csr``, one ``nonode_graph_build`` per edge tensor pair, cached th
 graph kernels of csrc/nonode_graph.hip walk. An index outside [0, n_nodes) raises ValueError at once for a
 host list; for a device list it goes through the same flag / ``finish()`` / deferred ValueError mechanism,
 with ``nonode_graph_build`` as the flag's writer (it drops the bad edge, so no kernel reads out of range).
+Training on such a list (``EGNO(graph="trainable")``) also needs the CSR by sender and, for a device list,
+the mask of the edges the build kept (``csr_by_sender``, cached per edge tensor pair as well).
 """
 from collections import OrderedDict
 
@@ -125,6 +127,7 @@ class _DeviceChecks:
         for k in keys:
             _checked.pop(k, None)
             _csr.pop(k, None)
+            _csr_sender.pop(k, None)
         self.in_flight, self.unconfirmed = [], []
         self.flag.zero_()
         self.host.zero_()
@@ -293,3 +296,47 @@ def csr(edge_index, n_nodes, device=None):
     while len(_csr) > _CACHE:
         _csr.popitem(last=False)
     return row_ptr, col, eid
+
+
+# the second CSR of the reverse pass (EGNO graph="trainable"), cached per edge tensor pair like _csr
+_csr_sender = OrderedDict()
+
+
+def csr_by_sender(edge_index, n_nodes, device=None):
+    """(srow_ptr [n_nodes + 1], seid [E], valid [E] or None) int32 device tensors for the reverse pass of
+    the graph layer: the same edge list as a CSR by SENDER (nonode_graph_build with rows and cols swapped;
+    each row ordered by (receiver, original index), seid the original edge index), and the mask of the
+    edges the build kept (None for a host list, which was range-checked: every edge is kept). Cached per
+    edge tensor pair, as csr is; a device list's bad index goes through csr's flag mechanism."""
+    rows, cols = _split(edge_index)
+    row_ptr, _, eid = csr(edge_index, n_nodes, device)   # checks, polls, and the receiver CSR's cache
+    dev = row_ptr.device
+    E = rows.numel()
+    key = _key(rows, cols, E, n_nodes) + (str(dev),)
+    hit = _csr_sender.get(key)
+    if hit is not None:
+        _csr_sender.move_to_end(key)
+        return hit[0], hit[1], hit[2]
+    from . import _lib
+    r, c = rows, cols
+    if r.dtype != c.dtype or r.dtype not in (torch.int32, torch.int64):
+        r, c = r.to(torch.int64), c.to(torch.int64)
+    r, c = r.to(dev).contiguous(), c.to(dev).contiguous()
+    srow_ptr = torch.empty(n_nodes + 1, dtype=torch.int32, device=dev)
+    scol = torch.empty(E, dtype=torch.int32, device=dev)
+    seid = torch.empty(E, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    ws_bytes = L.nonode_graph_workspace_bytes(E, n_nodes)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+    st = _state(dev)
+    s = _lib.stream_of(srow_ptr)
+    _lib.check(L.nonode_graph_build(_lib.ptr(c), _lib.ptr(r), r.element_size(), E, n_nodes, _lib.ptr(srow_ptr),
+                                    _lib.ptr(scol), _lib.ptr(seid), _lib.ptr(st.flag), _lib.ptr(ws), ws_bytes, s))
+    valid = None
+    if rows.is_cuda and E:
+        valid = torch.empty(E, dtype=torch.int32, device=dev)
+        _lib.check(L.nonode_graph_edge_mask(_lib.ptr(row_ptr), _lib.ptr(eid), n_nodes, E, _lib.ptr(valid), s))
+    _csr_sender[key] = (srow_ptr, seid, valid, rows, cols)
+    while len(_csr_sender) > _CACHE:
+        _csr_sender.popitem(last=False)
+    return srow_ptr, seid, valid

@@ -1,7 +1,7 @@
 """Timings of the general-graph path (EGNO graph="any", csrc/nonode_graph.hip) on the GPU. One JSON
 line per case on stdout (DESIGN.md section 3.7 quotes them; raw lines under profiles/graph/).
 
-python tools/bench_graph.py [--case price|knn|all] [--reps 7] [--iters 20]
+python tools/bench_graph.py [--case price|knn|knn_train|all] [--reps 7] [--iters 20] [--arm both|ours]
 
   price  the C2 graph (B = 512, N = 20, T = 10: 5120 fully connected graphs per layer launch) through
          the fused layer entry (nonode_egnn_layer) and, passed as an edge list, through the general one
@@ -13,6 +13,10 @@ python tools/bench_graph.py [--case price|knn|all] [--reps 7] [--iters 20]
          the edge walk's share of the fp16x3 ceiling from the layer's time as an upper bound on the edge
          walk's own (kernel times proper: rocprofv3 --kernel-trace --stats of this script, in a run of
          its own).
+  knn_train  the knn case trained: one forward + backward of EGNO(graph="trainable").train() (loss on x; every
+         parameter's gradient) against fp32 autograd of oracle/torch_ref.egno_forward on the same device,
+         alternated likewise. --arm ours runs the HIP arm alone (for a rocprofv3 --kernel-trace --stats run
+         of its own: the per-kernel split).
 Times are device events around `iters` back-to-back calls after a warm-up; each case reports the median
 over the reps and the spread (min, max) beside it.
 """
@@ -27,7 +31,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import no_node_comparison_amd as pkg  # noqa: E402
-from no_node_comparison_amd import _lib, graph  # noqa: E402
+from no_node_comparison_amd import _lib, autograd, graph  # noqa: E402
 from oracle import torch_ref as tr  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -188,15 +192,66 @@ def case_knn(args):
             "peak_basis": "dense fp16 MFMA peak / 3 (fp16x3 split products), as bench.py --full prices the fused layer"}
 
 
+def case_knn_train(args):
+    B, N, T, K = 8, 1000, 10, 16
+    m = model(T, graph="trainable").train()
+    loc, vel, q = synthetic(B, N, 2)
+    rows, cols = knn_graph(loc, K)
+    x, v = loc.reshape(-1, 3).contiguous(), vel.reshape(-1, 3).contiguous()
+    qq = q.reshape(-1, 1)
+    ef = torch.cat([qq[rows] * qq[cols], ((x[rows] - x[cols]) ** 2).sum(1, keepdim=True)], 1).contiguous()
+    h = torch.cat([v.norm(dim=1, keepdim=True), qq], 1).contiguous()
+    lm = loc.mean(1, keepdim=True).repeat(1, N, 1).reshape(-1, 3).contiguous()
+    t_out = torch.arange(1, T + 1, device=DEV).repeat(B, 1)
+    n, E = B * N, rows.numel()
+    target = x.repeat(T, 1) + 0.1
+    p32 = {k_: t.detach().float().clone().requires_grad_(True) for k_, t in m.state_dict().items()}
+    tf = t_out.float()
+
+    def ours():
+        m.zero_grad(set_to_none=True)
+        xo, _, _ = m(x, h, [rows, cols], ef, v=v, loc_mean=lm, timesteps_out=t_out)
+        ((xo - target) ** 2).mean().backward()
+
+    def ref():
+        for t in p32.values():
+            t.grad = None
+        with torch.device(DEV):   # (torch_ref's factory calls take the default device)
+            xo, _, _ = tr.egno_forward(p32, x, h, rows, cols, ef, v, lm, tf, T=T)
+        ((xo - target) ** 2).mean().backward()
+
+    arms = {"trainable": ours} if args.arm == "ours" else {"trainable": ours, "torch_ref": ref}
+    t = alternate(arms, args.reps, max(args.iters // 4, 3))
+    g = stats(t["trainable"])
+    res = {"case": "knn_train", "shape": {"graphs": B, "nodes_per_graph": N, "k": K, "T": T, "layers": 4, "E": E},
+           "trainable_fwd_bwd": g, "trainable_per_rep_ms": t["trainable"],
+           "frame_groups_per_layer": len(autograd.graph_frame_groups(T, E))}
+    if args.arm != "ours":
+        r = stats(t["torch_ref"])
+        ours()
+        ref()
+        torch.cuda.synchronize()
+        gerr = {k_: float((q_.grad - p32[k_].grad).abs().max() / p32[k_].grad.abs().max())
+                for k_, q_ in m.named_parameters() if p32[k_].grad is not None and float(p32[k_].grad.abs().max()) > 0}
+        # (the loss reads x alone: the last layer's node_net has no gradient in either arm)
+        res.update({"torch_ref_fp32_fwd_bwd": r, "torch_ref_per_rep_ms": t["torch_ref"],
+                    "speedup_over_torch_ref": r["median_ms"] / g["median_ms"],
+                    "speedup_per_rep": [b_ / a_ for a_, b_ in zip(t["trainable"], t["torch_ref"])],
+                    "faster_on_every_alternation": all(a_ < b_ for a_, b_ in zip(t["trainable"], t["torch_ref"])),
+                    "worst_grad_maxnorm_rel_vs_torch_ref_fp32": max(gerr.values())})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", default="all", choices=["price", "knn", "all"])
+    ap.add_argument("--case", default="all", choices=["price", "knn", "knn_train", "all"])
+    ap.add_argument("--arm", default="both", choices=["both", "ours"], help="knn_train: the HIP arm alone")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_graph.py measures on the GPU: no ROCm device found")
-    for name, fn in (("price", case_price), ("knn", case_knn)):
+    for name, fn in (("price", case_price), ("knn", case_knn), ("knn_train", case_knn_train)):
         if args.case in (name, "all"):
             res = fn(args)
             res["device"] = torch.cuda.get_device_name(0)
