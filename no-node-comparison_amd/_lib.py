@@ -275,6 +275,17 @@ def stream_of(t):
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
+def f32(t):
+    """t detached as a contiguous float32 tensor (no copy if it is one already); None stays None."""
+    return None if t is None else t.detach().to(torch.float32).contiguous()
+
+
+def alloc_outputs(rows, hidden_nf, ws_bytes, dev):
+    """(x_out [rows, 3], v_out [rows, 3], h_out [rows, hidden_nf], workspace of ws_bytes) of a model launch."""
+    return (torch.empty(rows, 3, device=dev), torch.empty(rows, 3, device=dev),
+            torch.empty(rows, hidden_nf, device=dev), torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev))
+
+
 def require_device(*tensors):
     for t in tensors:
         if t is not None and (not t.is_cuda):

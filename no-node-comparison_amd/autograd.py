@@ -15,8 +15,7 @@ import torch
 from . import _lib
 
 
-def _f32(t):
-    return t.detach().to(torch.float32).contiguous()
+_f32 = _lib.f32
 
 
 class EGNOTrain(torch.autograd.Function):
@@ -40,16 +39,12 @@ class EGNOTrain(torch.autograd.Function):
             ctx.frame_input = [0] * T if t_in is None else list(range(T))
         x, h, v, ef = _f32(x), _f32(h), _f32(v), _f32(edge_fea)
         tt = model._t_out_f32(t_out)   # cached per tensor / version: no int64 -> f32 copy per step
-        lm = _f32(loc_mean) if loc_mean is not None else None   # unused without time convolutions
+        lm = _f32(loc_mean)   # None: unused without time convolutions
         emb_cols = model.time_emb_dim * (1 if t_in is None else 2)
         Bt = tt.shape[0]
         blobs, tblobs = model._packed()
-        n = T * B * N
-        x_out = torch.empty(n, 3, device=dev)
-        v_out = torch.empty(n, 3, device=dev)
-        h_out = torch.empty(n, model.hidden_nf, device=dev)
         ws_bytes = L.nonode_egno_workspace_bytes(B, N, T, Bt)
-        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev)
+        x_out, v_out, h_out, ws = _lib.alloc_outputs(T * B * N, model.hidden_nf, ws_bytes, dev)
         st_bytes = L.nonode_egno_train_state_bytes(B, N, T, model.n_layers, model.in_node_nf, emb_cols)
         state = torch.empty((st_bytes + 3) // 4, dtype=torch.float32, device=dev)
         P = ctypes.c_void_p * model.n_layers
@@ -311,6 +306,58 @@ def _tconvx_lm_grad(gxo, gvo, txw, T, modes):
     return -spec.reshape(-1, 3)
 
 
+def _layer_tconv(model, i, BN, h, x, v, loc_mean, tblobs, s):
+    """The head of a per-layer tape node: TimeConv (+ TimeConv_x) of layer i on h [T*BN, 64], x, v
+    [T*BN, 3] (f32, contiguous; nonode_egno_tconv). Returns (loc_mean as f32, ht, xt, vt, v_out): the
+    EGNN layer's inputs and the v the node returns (the layer leaves v alone; without time convolutions
+    the inputs themselves and a copy of v)."""
+    if not model.use_time_conv:
+        return None, h, x, v, v.clone()
+    L = _lib.lib()
+    T = model.num_timesteps
+    n, dev = T * BN, h.device
+    lm = _f32(loc_mean)
+    tcx = _f32(model.time_conv_x_modules[i].t_conv.weights1)
+    ht, xt, vt = torch.empty(n, 64, device=dev), torch.empty(n, 3, device=dev), torch.empty(n, 3, device=dev)
+    _lib.check(L.nonode_egno_tconv(BN, T, model.num_modes, _lib.ptr(h), _lib.ptr(x), _lib.ptr(v), _lib.ptr(lm),
+                                   _lib.ptr(tblobs[i]), _lib.ptr(tcx), _lib.ptr(ht), _lib.ptr(xt), _lib.ptr(vt), s))
+    return lm, ht, xt, vt, vt
+
+
+def _layer_tconv_bwd(model, i, BN, h, x, v, lm, p_tw, p_txw, ght, gxt, gvt, want_lm, s):
+    """The tail of a per-layer tape node's backward: nonode_egno_tconv_bwd from the gradients ght, gxt, gvt
+    of the EGNN layer's inputs. Returns (g_h, g_x, g_v, g_loc_mean or None, g_weights1 of TimeConv and of
+    TimeConv_x in their parameters' dtypes)."""
+    L = _lib.lib()
+    T = model.num_timesteps
+    g_h, g_x, g_v = torch.empty_like(h), torch.empty_like(x), torch.empty_like(v)
+    tw, txw = _f32(p_tw), _f32(p_txw)      # kept alive over the call
+    g_tw, g_txw = torch.empty_like(tw), torch.empty_like(txw)
+    ws_bytes = L.nonode_egno_tconv_bwd_workspace_bytes(BN, T, model.num_modes)
+    ws = torch.empty((ws_bytes + 3) // 4, device=h.device)
+    _, tblobs = model._packed()
+    _lib.check(L.nonode_egno_tconv_bwd(BN, T, model.num_modes, _lib.ptr(h), _lib.ptr(x), _lib.ptr(v), _lib.ptr(lm),
+                                       _lib.ptr(tblobs[i]), _lib.ptr(tw), _lib.ptr(txw), _lib.ptr(ght),
+                                       _lib.ptr(gxt), _lib.ptr(gvt), _lib.ptr(g_h), _lib.ptr(g_x), _lib.ptr(g_v),
+                                       _lib.ptr(g_tw), _lib.ptr(g_txw), _lib.ptr(ws), ws_bytes, s))
+    sink = getattr(model, "_train_bwd_sink", None)
+    if sink is not None:   # tests: the workspace head holds the LeakyReLU decisions the reverse used
+        sink.append((i, ws))
+    g_lm = _tconvx_lm_grad(gxt, gvt, txw, T, model.num_modes) if want_lm else None
+    return g_h, g_x, g_v, g_lm, g_tw.to(p_tw.dtype), g_txw.to(p_txw.dtype)
+
+
+def _layer_tape(model, node, head, hh, xx, vv, lm, edge_fea):
+    """One tape node `node` (FlatLayerTrain / GraphLayerTrain, called with (model, i, *head, h, x, v, loc_mean,
+    edge_fea, *layer parameters)) per layer; returns (x, v, h) as EGNO.forward does."""
+    for i in range(model.n_layers):
+        params = _flat_layer_params(model, i)
+        if model.use_time_conv:
+            params += [model.time_conv_modules[i].t_conv.weights1, model.time_conv_x_modules[i].t_conv.weights1]
+        hh, xx, vv = node.apply(model, i, *head, hh, xx, vv, lm, edge_fea, *params)
+    return xx, vv, hh
+
+
 class FlatLayerTrain(torch.autograd.Function):
     """TimeConv (+ TimeConv_x) of layer i, then its flat EGNN layer (egno.py:99-111 with flat=True)."""
 
@@ -319,19 +366,11 @@ class FlatLayerTrain(torch.autograd.Function):
         L = _lib.lib()
         T = model.num_timesteps
         dev = h.device
-        BN, n = B * N, T * B * N
+        n = T * B * N
         h, x, v, ef = _f32(h), _f32(x), _f32(v), _f32(ef)
         blobs, tblobs = model._packed()
         s = _lib.stream_of(h)
-        if model.use_time_conv:
-            lm = _f32(loc_mean)
-            tcx = _f32(model.time_conv_x_modules[i].t_conv.weights1)
-            ht, xt, vt = torch.empty(n, 64, device=dev), torch.empty(n, 3, device=dev), torch.empty(n, 3, device=dev)
-            _lib.check(L.nonode_egno_tconv(BN, T, model.num_modes, _lib.ptr(h), _lib.ptr(x), _lib.ptr(v), _lib.ptr(lm),
-                                           _lib.ptr(tblobs[i]), _lib.ptr(tcx), _lib.ptr(ht), _lib.ptr(xt), _lib.ptr(vt),
-                                           s))
-        else:
-            lm, ht, xt, vt = None, h, x, v
+        lm, ht, xt, vt, v_out = _layer_tconv(model, i, B * N, h, x, v, loc_mean, tblobs, s)
         state = torch.empty(L.nonode_egnn_layer_flat_state_floats(T * B, N), device=dev)
         h_out, x_out = torch.empty(n, 64, device=dev), torch.empty(n, 3, device=dev)
         _lib.check(L.nonode_egnn_layer_flat(T * B, N, model.in_edge_nf, B, _lib.ptr(ht), _lib.ptr(xt), _lib.ptr(vt),
@@ -341,7 +380,7 @@ class FlatLayerTrain(torch.autograd.Function):
         ctx.model, ctx.i, ctx.B, ctx.N = model, i, B, N
         ctx.keep = (h, x, v, lm, ef, ht, xt, vt, state)
         ctx.save_for_backward(*params)
-        return h_out, x_out, vt.clone() if vt is v else vt
+        return h_out, x_out, v_out
 
     @staticmethod
     def backward(ctx, gh, gx, gv):
@@ -358,7 +397,7 @@ class FlatLayerTrain(torch.autograd.Function):
         gx = _f32(gx) if gx is not None else z(3)
         gv = _f32(gv) if gv is not None else z(3)
         blobs, _ = model._packed()
-        bb = model._packed_flat_bwd()
+        bb = model._packed_bwd()
         nops = torch.empty(n, _FN["STRIDE"], device=dev)
         eops = torch.empty(E, _FE["STRIDE"], device=dev)
         gvt = torch.empty(n, 3, device=dev)
@@ -392,22 +431,9 @@ class FlatLayerTrain(torch.autograd.Function):
         grads = [g.reshape(p.shape).to(p.dtype) for g, p in zip(grads, params[:16])]
         if not model.use_time_conv:
             return (None,) * 4 + (ght, gxt, gvt, None, None) + tuple(grads)
-        g_h, g_x, g_v = torch.empty_like(h), torch.empty_like(x), torch.empty_like(v)
-        tw, txw = _f32(params[16]), _f32(params[17])      # kept alive over the call
-        g_tw, g_txw = torch.empty_like(tw), torch.empty_like(txw)
-        ws_bytes = L.nonode_egno_tconv_bwd_workspace_bytes(B * N, T, model.num_modes)
-        ws = torch.empty((ws_bytes + 3) // 4, device=dev)
-        _, tblobs = model._packed()
-        _lib.check(L.nonode_egno_tconv_bwd(B * N, T, model.num_modes, _lib.ptr(h), _lib.ptr(x), _lib.ptr(v), _lib.ptr(lm),
-                                           _lib.ptr(tblobs[i]), _lib.ptr(tw), _lib.ptr(txw), _lib.ptr(ght),
-                                           _lib.ptr(gxt), _lib.ptr(gvt), _lib.ptr(g_h), _lib.ptr(g_x), _lib.ptr(g_v),
-                                           _lib.ptr(g_tw), _lib.ptr(g_txw), _lib.ptr(ws), ws_bytes, s))
-        sink = getattr(model, "_train_bwd_sink", None)
-        if sink is not None:   # tests: the workspace head holds the LeakyReLU decisions the reverse used
-            sink.append((i, ws))
-        g_lm = _tconvx_lm_grad(gxt, gvt, txw, T, model.num_modes) if ctx.needs_input_grad[7] else None
-        return (None,) * 4 + (g_h, g_x, g_v, g_lm, None) + tuple(grads) + (g_tw.to(params[16].dtype),
-                                                                             g_txw.to(params[17].dtype))
+        tail = _layer_tconv_bwd(model, i, B * N, h, x, v, lm, params[16], params[17], ght, gxt, gvt,
+                                ctx.needs_input_grad[7], s)
+        return (None,) * 4 + tail[:4] + (None,) + tuple(grads) + tail[4:]
 
 
 def _embed_frames(model, x, h, v, loc_mean, t_out, BN):
@@ -435,12 +461,7 @@ def egno_flat_train(model, x, h, edge_fea, v, loc_mean, t_out, B, N):
     """EGNO(flat=True).forward in training (egno.py:37-111, num_inputs == 1): the time embedding and the
     embedding Linear as torch ops, then one FlatLayerTrain node per layer."""
     hh, xx, vv, lm = _embed_frames(model, x, h, v, loc_mean, t_out, B * N)
-    for i in range(model.n_layers):
-        params = _flat_layer_params(model, i)
-        if model.use_time_conv:
-            params += [model.time_conv_modules[i].t_conv.weights1, model.time_conv_x_modules[i].t_conv.weights1]
-        hh, xx, vv = FlatLayerTrain.apply(model, i, B, N, hh, xx, vv, lm, edge_fea, *params)
-    return xx, vv, hh
+    return _layer_tape(model, FlatLayerTrain, (B, N), hh, xx, vv, lm, edge_fea)
 
 
 # ---- EGNO(graph="trainable") training on any edge list (csrc/nonode_graph_train.hip) ------------------
@@ -552,15 +573,7 @@ class GraphLayerTrain(torch.autograd.Function):
         h, x, v, ef = _f32(h), _f32(x), _f32(v), _f32(ef)
         blobs, tblobs = model._packed()
         s = _lib.stream_of(h)
-        if model.use_time_conv:
-            lm = _f32(loc_mean)
-            tcx = _f32(model.time_conv_x_modules[i].t_conv.weights1)
-            ht, xt, vt = torch.empty(nt, 64, device=dev), torch.empty(nt, 3, device=dev), torch.empty(nt, 3, device=dev)
-            _lib.check(L.nonode_egno_tconv(n, T, model.num_modes, _lib.ptr(h), _lib.ptr(x), _lib.ptr(v), _lib.ptr(lm),
-                                           _lib.ptr(tblobs[i]), _lib.ptr(tcx), _lib.ptr(ht), _lib.ptr(xt), _lib.ptr(vt),
-                                           s))
-        else:
-            lm, ht, xt, vt = None, h, x, v
+        lm, ht, xt, vt, v_out = _layer_tconv(model, i, n, h, x, v, loc_mean, tblobs, s)
         row_ptr, col, eid = graph[0]
         st_bytes = L.nonode_egnn_layer_graph_workspace_bytes(T, n)
         state = torch.empty((st_bytes + 3) // 4, device=dev)   # the layer's workspace is the saved state
@@ -573,7 +586,7 @@ class GraphLayerTrain(torch.autograd.Function):
         ctx.model, ctx.i, ctx.n, ctx.E, ctx.graph = model, i, n, E, graph
         ctx.keep = (h, x, v, lm, ef, ht, xt, vt, state)
         ctx.save_for_backward(*params)
-        return h_out, x_out, vt.clone() if vt is v else vt
+        return h_out, x_out, v_out
 
     @staticmethod
     def backward(ctx, gh, gx, gv):
@@ -581,12 +594,10 @@ class GraphLayerTrain(torch.autograd.Function):
         params = ctx.saved_tensors   # raises if a parameter changed in place since the forward
         h, x, v, lm, ef, ht, xt, vt, state = ctx.keep
         ctx.keep = None
-        L = _lib.lib()
-        T = model.num_timesteps
-        dev = h.device
-        gh, gx, gv = (_f32(g) if g is not None else None for g in (gh, gx, gv))
-        blobs, tblobs = model._packed()
+        gh, gx, gv = _f32(gh), _f32(gx), _f32(gv)
+        blobs, _ = model._packed()
         bb = model._packed_bwd()
+        T = model.num_timesteps
         ght, gxt, gvt, grads = graph_layer_reverse(T, n, E, model.in_edge_nf, 1, ht, xt, vt, ef, blobs[i], bb[i], state,
                                                    ctx.graph[0], ctx.graph[1], gx, gv, gh,
                                                    getattr(model, "graph_ops_cap_bytes", None),
@@ -594,21 +605,9 @@ class GraphLayerTrain(torch.autograd.Function):
         grads = [g.reshape(p.shape).to(p.dtype) for g, p in zip(grads, params[:16])] if grads else [None] * 16
         if not model.use_time_conv:
             return (None,) * 5 + (ght, gxt, gvt, None, None) + tuple(grads)
-        g_h, g_x, g_v = torch.empty_like(h), torch.empty_like(x), torch.empty_like(v)
-        tw, txw = _f32(params[16]), _f32(params[17])      # kept alive over the call
-        g_tw, g_txw = torch.empty_like(tw), torch.empty_like(txw)
-        ws_bytes = L.nonode_egno_tconv_bwd_workspace_bytes(n, T, model.num_modes)
-        ws = torch.empty((ws_bytes + 3) // 4, device=dev)
-        _lib.check(L.nonode_egno_tconv_bwd(n, T, model.num_modes, _lib.ptr(h), _lib.ptr(x), _lib.ptr(v), _lib.ptr(lm),
-                                           _lib.ptr(tblobs[i]), _lib.ptr(tw), _lib.ptr(txw), _lib.ptr(ght),
-                                           _lib.ptr(gxt), _lib.ptr(gvt), _lib.ptr(g_h), _lib.ptr(g_x), _lib.ptr(g_v),
-                                           _lib.ptr(g_tw), _lib.ptr(g_txw), _lib.ptr(ws), ws_bytes, _lib.stream_of(h)))
-        sink = getattr(model, "_train_bwd_sink", None)
-        if sink is not None:   # tests: the workspace head holds the LeakyReLU decisions the reverse used
-            sink.append((i, ws))
-        g_lm = _tconvx_lm_grad(gxt, gvt, txw, T, model.num_modes) if ctx.needs_input_grad[8] else None
-        return (None,) * 5 + (g_h, g_x, g_v, g_lm, None) + tuple(grads) + (g_tw.to(params[16].dtype),
-                                                                             g_txw.to(params[17].dtype))
+        tail = _layer_tconv_bwd(model, i, n, h, x, v, lm, params[16], params[17], ght, gxt, gvt,
+                                ctx.needs_input_grad[8], _lib.stream_of(h))
+        return (None,) * 5 + tail[:4] + (None,) + tuple(grads) + tail[4:]
 
 
 def egno_graph_train(model, x, h, edge_index, edge_fea, v, loc_mean, t_out):
@@ -620,9 +619,4 @@ def egno_graph_train(model, x, h, edge_index, edge_fea, v, loc_mean, t_out):
     csr = _graph.csr(edge_index, n, device=x.device)
     scsr = _graph.csr_by_sender(edge_index, n, device=x.device)
     hh, xx, vv, lm = _embed_frames(model, x, h, v, loc_mean, t_out, n)
-    for i in range(model.n_layers):
-        params = _flat_layer_params(model, i)
-        if model.use_time_conv:
-            params += [model.time_conv_modules[i].t_conv.weights1, model.time_conv_x_modules[i].t_conv.weights1]
-        hh, xx, vv = GraphLayerTrain.apply(model, i, n, E, (csr, scsr), hh, xx, vv, lm, edge_fea, *params)
-    return xx, vv, hh
+    return _layer_tape(model, GraphLayerTrain, (n, E, (csr, scsr)), hh, xx, vv, lm, edge_fea)

@@ -2188,52 +2188,24 @@ namespace {
 // nonode_flat.hip (included at the end of this unit): one EGNN layer with flat=True
 int launch_flat_layer(int n_graphs, int N, int ne, int ef_mod, const float* h, const float* x, const float* v,
                       const float* ef, const float* blob, float* h_out, float* x_out, float* ws, hipStream_t s);
-// flat: the blobs are flat-layer blobs (nonode_pack_layer_flat), the workspace has the flat layer's
-// n x 580 floats after the common part (nonode_egno_flat_workspace_bytes)
-int egno_forward_impl(int frames, int flat, int B, int N, int T, int n_layers, int in_node, int n_edge_feat,
-                        int time_emb_dim, int modes, int Bt,
-                        const float* x, const float* h, const float* v, const float* loc_mean,
-                        const float* edge_fea, const float* t_in, const float* t_out,
-                        const float* emb_w, const float* emb_b,
-                        const float* const* blobs, const float* const* tconv_blobs,
-                        const float* const* tconvx_w,
-                        float* x_out, float* v_out, float* h_out,
-                        void* workspace, size_t workspace_bytes, void* stream) {
-  if (B <= 0 || N < 2 || T <= 0 || T > TMAX || n_layers < 1 || in_node < 0 || in_node > 8 ||
-      modes < 1 || modes > MMAX || time_emb_dim < 4 || time_emb_dim > 64 || (time_emb_dim & 1) ||
-      Bt <= 0 || (B * N) % Bt != 0)
-    return fail(NONODE_EUNSUPPORTED,
-                "egno_forward: B=%d N=%d T=%d layers=%d in_node=%d modes=%d temb=%d Bt=%d", B, N, T,
-                n_layers, in_node, modes, time_emb_dim, Bt);
-  // use_time_conv=False (egno.py:99-107 skipped): both TimeConv arrays null
-  const bool tc = tconv_blobs != nullptr;
-  if (!x || !h || !v || (tc && !loc_mean) || !t_out || !emb_w || !emb_b || !blobs || tc != (tconvx_w != nullptr) ||
-      !x_out || !v_out || !h_out || !workspace)
-    return fail(NONODE_EINVAL, "egno_forward: null pointer");
-  const size_t ws_need = flat ? nonode_egno_flat_workspace_bytes(B, N, T, Bt) : nonode_egno_workspace_bytes(B, N, T, Bt);
-  if (workspace_bytes < ws_need)
-    return fail(NONODE_EINVAL, "egno_forward: workspace %zu < %zu", workspace_bytes, ws_need);
-  hipStream_t s = (hipStream_t)stream;
-  const int BN = B * N;
+// The model's sequence after an entry's own validation, on BN node columns (egno.py:84-107): the
+// time-embedding table, then per layer TimeConv and layer(l, h_in, x_in, h_out, x_out) -> status. The
+// workspace starts with h | x | embedding table (nonode_egno_workspace_bytes).
+template <typename Layer>
+int egno_forward_seq(int frames, int BN, int T, int n_layers, int in_node, int time_emb_dim, int modes, int Bt,
+                     const float* x, const float* h, const float* v, const float* loc_mean, const float* t_in,
+                     const float* t_out, const float* emb_w, const float* emb_b, const float* const* tconv_blobs,
+                     const float* const* tconvx_w, float* x_out, float* v_out, float* h_out, void* workspace,
+                     hipStream_t s, Layer layer) {
   const size_t n = (size_t)BN * T;
   float* hB = (float*)workspace;
   float* xB = hB + n * 64;
   float* etab = xB + n * 3;
   const int emb_ld = in_node + (t_in ? 2 : 1) * time_emb_dim;
-  float* flat_ws = (float*)((char*)workspace + flat_ws_offset(B, N, T, Bt));
-  auto layer = [&](int l, const float* hi, const float* xi, float* ho, float* xo) {
-    if (flat)
-      return launch_flat_layer(T * B, N, n_edge_feat, frames ? T * B : B, hi, xi, v_out, edge_fea, blobs[l], ho, xo,
-                               flat_ws, s);
-    return launch_layer<EGNO>(T * B, N, n_edge_feat, frames ? T * B : B, hi, xi, v_out, edge_fea, blobs[l], 0.f, 1.f,
-                              0, ho, xo, nullptr, s, 1, nullptr, nullptr, nullptr, BN);
-  };
-  {
-    hipLaunchKernelGGL(temb_kernel, dim3((Bt * T + TEMB_ROWS - 1) / TEMB_ROWS), dim3(256), 0, s, Bt, T, in_node, time_emb_dim,
-                       t_out, emb_w, emb_ld, emb_b, etab, t_in);
-    if (int rc = check_launch("temb_kernel")) return rc;
-  }
-  if (!tc) {
+  hipLaunchKernelGGL(temb_kernel, dim3((Bt * T + TEMB_ROWS - 1) / TEMB_ROWS), dim3(256), 0, s, Bt, T, in_node, time_emb_dim,
+                     t_out, emb_w, emb_ld, emb_b, etab, t_in);
+  if (int rc = check_launch("temb_kernel")) return rc;
+  if (!tconv_blobs) {
     // layer l reads buffer (L - l) & 1 and writes (L - 1 - l) & 1 of {h_out | x_out, hB | xB}, so the
     // last layer writes h_out, x_out; v (unchanged by EGNN_Layer, basic.py:186) is replicated once
     float* hb[2] = {h_out, hB};
@@ -2261,6 +2233,65 @@ int egno_forward_impl(int frames, int flat, int B, int N, int T, int n_layers, i
     }
     if (int rc = launch_tconv(l == 0, a, s)) return rc;
     if (int rc = layer(l, hB, xB, h_out, x_out)) return rc;
+  }
+  return NONODE_OK;
+}
+// flat: the blobs are flat-layer blobs (nonode_pack_layer_flat), the workspace has the flat layer's
+// n x 580 floats after the common part (nonode_egno_flat_workspace_bytes)
+int egno_forward_impl(int frames, int flat, int B, int N, int T, int n_layers, int in_node, int n_edge_feat,
+                        int time_emb_dim, int modes, int Bt,
+                        const float* x, const float* h, const float* v, const float* loc_mean,
+                        const float* edge_fea, const float* t_in, const float* t_out,
+                        const float* emb_w, const float* emb_b,
+                        const float* const* blobs, const float* const* tconv_blobs,
+                        const float* const* tconvx_w,
+                        float* x_out, float* v_out, float* h_out,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  if (B <= 0 || N < 2 || T <= 0 || T > TMAX || n_layers < 1 || in_node < 0 || in_node > 8 ||
+      modes < 1 || modes > MMAX || time_emb_dim < 4 || time_emb_dim > 64 || (time_emb_dim & 1) ||
+      Bt <= 0 || (B * N) % Bt != 0)
+    return fail(NONODE_EUNSUPPORTED,
+                "egno_forward: B=%d N=%d T=%d layers=%d in_node=%d modes=%d temb=%d Bt=%d", B, N, T,
+                n_layers, in_node, modes, time_emb_dim, Bt);
+  // use_time_conv=False (egno.py:99-107 skipped): both TimeConv arrays null
+  const bool tc = tconv_blobs != nullptr;
+  if (!x || !h || !v || (tc && !loc_mean) || !t_out || !emb_w || !emb_b || !blobs || tc != (tconvx_w != nullptr) ||
+      !x_out || !v_out || !h_out || !workspace)
+    return fail(NONODE_EINVAL, "egno_forward: null pointer");
+  const size_t ws_need = flat ? nonode_egno_flat_workspace_bytes(B, N, T, Bt) : nonode_egno_workspace_bytes(B, N, T, Bt);
+  if (workspace_bytes < ws_need)
+    return fail(NONODE_EINVAL, "egno_forward: workspace %zu < %zu", workspace_bytes, ws_need);
+  hipStream_t s = (hipStream_t)stream;
+  const int BN = B * N;
+  float* flat_ws = (float*)((char*)workspace + flat_ws_offset(B, N, T, Bt));
+  auto layer = [&](int l, const float* hi, const float* xi, float* ho, float* xo) {
+    if (flat)
+      return launch_flat_layer(T * B, N, n_edge_feat, frames ? T * B : B, hi, xi, v_out, edge_fea, blobs[l], ho, xo,
+                               flat_ws, s);
+    return launch_layer<EGNO>(T * B, N, n_edge_feat, frames ? T * B : B, hi, xi, v_out, edge_fea, blobs[l], 0.f, 1.f,
+                              0, ho, xo, nullptr, s, 1, nullptr, nullptr, nullptr, BN);
+  };
+  return egno_forward_seq(frames, BN, T, n_layers, in_node, time_emb_dim, modes, Bt, x, h, v, loc_mean, t_in, t_out, emb_w,
+                          emb_b, tconv_blobs, tconvx_w, x_out, v_out, h_out, workspace, s, layer);
+}
+// The two SEGNO step entries' prologue: the embedding when no h_in is given (*hc = the h the substeps
+// start from) and, for T == 0, the copies that are the whole step (*done)
+int segno_step_prologue(size_t n, int T, int in_node, const float* his, const float* h_in, const float* x,
+                        const float* v, const float* emb_w, const float* emb_b, float* hemb, float* x_out, float* v_out,
+                        float* h_out, hipStream_t s, const float** hc, bool* done) {
+  *hc = h_in;
+  *done = T == 0;
+  if (!h_in) {
+    hipLaunchKernelGGL(embed_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, s, (int)n, in_node,
+                       his, emb_w, emb_b, hemb);
+    if (int rc = check_launch("embed_kernel")) return rc;
+    *hc = hemb;
+  }
+  if (T == 0) {
+    hipMemcpyAsync(h_out, *hc, n * 64 * sizeof(float), hipMemcpyDeviceToDevice, s);
+    hipMemcpyAsync(x_out, x, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s);
+    hipMemcpyAsync(v_out, v, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s);
+    return check_launch("segno T=0 copy");
   }
   return NONODE_OK;
 }
@@ -2333,19 +2364,11 @@ int nonode_segno_forward_step(int B, int N, int T, int in_node, int n_edge_feat,
   float* hemb = (float*)workspace;
   float* pp[6] = {hemb + n * 64, hemb + 2 * n * 64, hemb + 3 * n * 64, hemb + 3 * n * 64 + n * 3,
                   hemb + 3 * n * 64 + 2 * n * 3, hemb + 3 * n * 64 + 3 * n * 3};
-  const float* hc = h_in;
-  if (!hc) {
-    hipLaunchKernelGGL(embed_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, s, (int)n, in_node,
-                       his, emb_w, emb_b, hemb);
-    if (int rc = check_launch("embed_kernel")) return rc;
-    hc = hemb;
-  }
-  if (T == 0) {
-    hipMemcpyAsync(h_out, hc, n * 64 * sizeof(float), hipMemcpyDeviceToDevice, s);
-    hipMemcpyAsync(x_out, x, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s);
-    hipMemcpyAsync(v_out, v, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s);
-    return check_launch("segno T=0 copy");
-  }
+  const float* hc;
+  bool done;
+  if (int rc = segno_step_prologue(n, T, in_node, his, h_in, x, v, emb_w, emb_b, hemb, x_out, v_out, h_out, s, &hc, &done))
+    return rc;
+  if (done) return NONODE_OK;
   // all T substeps in one launch: each workgroup owns whole samples, so substep t+1 only needs
   // its own workgroup's substep-t results (model.py:95-102, gcl.py:111-119)
   return launch_layer<SEGNO>(B, N, n_edge_feat, B, hc, x, v, edge_attr, blob, 1.0f / (float)T, coords_weight,
@@ -2381,49 +2404,15 @@ int nonode_egno_forward_graph(int n_nodes, long long E, int T, int n_layers, int
     return fail(NONODE_EINVAL, "egno_forward_graph: workspace %zu < %zu", workspace_bytes,
                 nonode_egno_graph_workspace_bytes(n_nodes, T, Bt));
   hipStream_t s = (hipStream_t)stream;
-  const int BN = n_nodes, frames = t_in ? 1 : 0;
-  const size_t n = (size_t)BN * T;
-  float* hB = (float*)workspace;
-  float* xB = hB + n * 64;
-  float* etab = xB + n * 3;
+  const int frames = t_in ? 1 : 0;
   float* lws = (float*)((char*)workspace + align256(nonode_egno_workspace_bytes(1, n_nodes, T, Bt)));
-  const int emb_ld = in_node + (t_in ? 2 : 1) * time_emb_dim;
   // frame f owns node rows f n_nodes .. and shares the one CSR (egno.py:84-96); v is unchanged by the layer
   auto layer = [&](int l, const float* hi, const float* xi, float* ho, float* xo) {
     return nonode_tu::graph_layer(NONODE_VARIANT_EGNO, T, n_nodes, E, n_edge_feat, frames ? T : 1, hi, xi, v_out,
                                   edge_fea, blobs[l], row_ptr, col, eid, 0.f, 1.f, 0, ho, xo, nullptr, lws, s);
   };
-  hipLaunchKernelGGL(temb_kernel, dim3((Bt * T + TEMB_ROWS - 1) / TEMB_ROWS), dim3(256), 0, s, Bt, T, in_node,
-                     time_emb_dim, t_out, emb_w, emb_ld, emb_b, etab, t_in);
-  if (int rc = check_launch("temb_kernel")) return rc;
-  if (!tc) {   // as egno_forward_impl: layer l reads buffer (L - l) & 1 and writes (L - 1 - l) & 1
-    float* hb[2] = {h_out, hB};
-    float* xb[2] = {x_out, xB};
-    const int L = n_layers;
-    hipLaunchKernelGGL(h0_kernel, dim3((BN * 64 + 255) / 256), dim3(256), 0, s, BN, T, in_node, Bt, h, emb_w, emb_ld,
-                       etab, x, v, hb[L & 1], xb[L & 1], v_out, frames);
-    if (int rc = check_launch("h0_kernel")) return rc;
-    for (int l = 0; l < L; ++l) {
-      const int i = (L - l) & 1, o = (L - 1 - l) & 1;
-      if (int rc = layer(l, hb[i], xb[i], hb[o], xb[o])) return rc;
-    }
-    return NONODE_OK;
-  }
-  for (int l = 0; l < n_layers; ++l) {
-    TconvArgs a{};
-    a.BN = BN; a.T = T; a.M = effective_modes(T, modes); a.Mfull = modes;
-    a.wp = tconv_blobs[l]; a.wx = tconvx_w[l]; a.frames = frames;
-    a.h_out = hB; a.x_out = xB; a.v_out = v_out;
-    if (l == 0) {
-      a.h = nullptr; a.x = x; a.v = v; a.lm = loc_mean;
-      a.hin = h; a.din = in_node; a.emb_w = emb_w; a.emb_ld = emb_ld; a.etab = etab; a.Bt = Bt;
-    } else {
-      a.h = h_out; a.x = x_out; a.v = v_out; a.lm = loc_mean;
-    }
-    if (int rc = launch_tconv(l == 0, a, s)) return rc;
-    if (int rc = layer(l, hB, xB, h_out, x_out)) return rc;
-  }
-  return NONODE_OK;
+  return egno_forward_seq(frames, n_nodes, T, n_layers, in_node, time_emb_dim, modes, Bt, x, h, v, loc_mean, t_in, t_out,
+                          emb_w, emb_b, tconv_blobs, tconvx_w, x_out, v_out, h_out, workspace, s, layer);
 }
 
 size_t nonode_segno_graph_workspace_bytes(int n_nodes) {
@@ -2451,19 +2440,11 @@ int nonode_segno_forward_step_graph(int n_nodes, long long E, int T, int in_node
   float* ppx[2] = {hemb + 3 * n * 64, hemb + 3 * n * 64 + n * 3};
   float* ppv[2] = {hemb + 3 * n * 64 + 2 * n * 3, hemb + 3 * n * 64 + 3 * n * 3};
   float* lws = (float*)((char*)workspace + align256(nonode_segno_workspace_bytes(1, n_nodes)));
-  const float* hc = h_in;
-  if (!hc) {
-    hipLaunchKernelGGL(embed_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, s, n_nodes, in_node, his,
-                       emb_w, emb_b, hemb);
-    if (int rc = check_launch("embed_kernel")) return rc;
-    hc = hemb;
-  }
-  if (T == 0) {
-    hipMemcpyAsync(h_out, hc, n * 64 * sizeof(float), hipMemcpyDeviceToDevice, s);
-    hipMemcpyAsync(x_out, x, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s);
-    hipMemcpyAsync(v_out, v, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s);
-    return check_launch("segno T=0 copy");
-  }
+  const float* hc;
+  bool done;
+  if (int rc = segno_step_prologue(n, T, in_node, his, h_in, x, v, emb_w, emb_b, hemb, x_out, v_out, h_out, s, &hc, &done))
+    return rc;
+  if (done) return NONODE_OK;
   // T substeps of the shared layer with the edge attributes frozen (model.py:95-102), dt = 1/T
   const float* hi = hc; const float* xi = x; const float* vi = v;
   for (int t = 0; t < T; ++t) {

@@ -1,6 +1,7 @@
 // nonode_bwd_common.h — shared by the training translation units (nonode_train.hip, included by
-// nonode.hip, and nonode_node.hip): the backward weight-blob layout, true-scale SiLU helpers, the
-// power-of-two column scaling of the fp16x3 gradient products, and the node-backward interface.
+// nonode.hip; nonode_node.hip; nonode_tconv.hip; and, through nonode_graph_common.h, the two
+// general-graph units): the backward weight-blob layout, true-scale SiLU helpers, the small row
+// helpers, the column-scaled fp16x3 product of the gradient paths, and the node-backward interface.
 #pragma once
 #include "nonode_common.h"
 
@@ -62,6 +63,14 @@ __device__ __forceinline__ void zero4(f4 (&a)[4]) {
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) a[mt] = f4{0.f, 0.f, 0.f, 0.f};
 }
+__device__ __forceinline__ void scale4(f4 (&d)[4], const f4 (&a)[4], float s) {
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) d[mt] = a[mt] * s;
+}
+__device__ __forceinline__ void mul4(f4 (&g)[4], const f4 (&d)[4]) {
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) g[mt] *= d[mt];
+}
 // a = SiLU(z) keeping the sigmoid s for the reverse pass (one exp + one rcp per value, not two)
 __device__ __forceinline__ void silu_keep(const f4 (&z)[4], f4 (&s)[4], f4 (&a)[4]) {
 #pragma unroll
@@ -114,6 +123,47 @@ __device__ __forceinline__ float amax16(const f4 (&x)[4]) {
   for (int mt = 0; mt < 4; ++mt)
     m[mt] = fmaxf(fmaxf(fabsf(x[mt][0]), fabsf(x[mt][1])), fmaxf(fabsf(x[mt][2]), fabsf(x[mt][3])));
   return fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3]));
+}
+// column-scaled fp16x3 split of a 16-column operand (lane (e, g) holds column e; cm = its column max,
+// col_max(amax16(x)) when not given); returns the inverse scale
+__device__ __forceinline__ float cs_split(const f4 (&x)[4], h8 (&xh)[2], h8 (&xl)[2], float cm) {
+  const float sc = p2scale(cm);
+  f4 xs[4];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) xs[mt] = x[mt] * sc;
+  h16_split(xs, xh, xl);
+  return 1.f / sc;   // exact (power of two)
+}
+__device__ __forceinline__ float cs_split(const f4 (&x)[4], h8 (&xh)[2], h8 (&xl)[2]) {
+  return cs_split(x, xh, xl, col_max(amax16(x)));
+}
+// out (+)= inv * W x from a split (W: one fp16 hi/lo fragment set)
+template <bool ADD>
+__device__ __forceinline__ void mm_cs(f4 (&out)[4], const h8* wh, const h8 (&xh)[2], const h8 (&xl)[2], float inv,
+                                      int lane, unsigned us) {
+  f4 acc[4];
+  zero4(acc);
+  mfma_h16(acc, wh, xh, xl, lane, us);
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) out[mt] = ADD ? out[mt] + acc[mt] * inv : acc[mt] * inv;
+}
+// out += W x for a gradient column set x: each column scaled to [2^11, 2^12) before the split, the
+// product scaled back. The same arithmetic as cs_split + mm_cs<true>, written out: the statement order
+// is the one the fused edge backward (nonode_train.hip) is scheduled and register-allocated from
+__device__ __forceinline__ void mm64_cs(f4 (&out)[4], const h8* wh, const f4 (&x)[4], int lane, unsigned us, float cm) {
+  const float sc = p2scale(cm);
+  const float inv = 1.f / sc;   // exact (power of two)
+  f4 xs[4], acc[4];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) { xs[mt] = x[mt] * sc; acc[mt] = f4{0.f, 0.f, 0.f, 0.f}; }
+  h8 xh[2], xl[2];
+  h16_split(xs, xh, xl);
+  mfma_h16(acc, wh, xh, xl, lane, us);
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) out[mt] += acc[mt] * inv;
+}
+__device__ __forceinline__ void mm64_cs(f4 (&out)[4], const h8* wh, const f4 (&x)[4], int lane, unsigned us) {
+  mm64_cs(out, wh, x, lane, us, col_max(amax16(x)));
 }
 // max over the 16 lanes of a row (DPP: quad swaps, half-row and row mirrors; no LDS round trip)
 template <int C>

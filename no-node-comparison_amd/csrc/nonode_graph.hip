@@ -1,10 +1,12 @@
 // The E(n)-equivariant layer on an explicit edge list (EGNN_Layer.forward, basic.py:167-186;
 // SEGNO_GCL.forward, gcl.py:111-119, for any `edges`): inference on gfx950.
 //
-// A translation unit of its own, so the fused fully connected kernels of nonode.hip compile exactly as
-// before. It reads the packed layer blob of nonode_pack_layer unchanged (fp16 hi/lo fragments for the
-// fp16x3 products, f32 fragments for the range guard's exact path, the scalar-input k-steps, the
-// log2-domain SiLU scalings) and keeps the fused kernel's arithmetic per edge.
+// A translation unit of its own (built with the default machine scheduler). It reads the packed layer
+// blob of nonode_pack_layer unchanged (fp16 hi/lo fragments for the fp16x3 products, f32 fragments for
+// the range guard's exact path, the scalar-input k-steps, the log2-domain SiLU scalings) and keeps the
+// fused kernel's arithmetic per edge. The tile indexing, the CSR row walk, the edge step and the node
+// step's pre-activations are nonode_graph_common.h's, which the reverse pass (nonode_graph_train.hip)
+// calls as well.
 //
 //   graph_*_kernel (build)  the edge list as a CSR by receiver, rows ordered by (sender, original
 //                           index): a pure function of the edge set
@@ -16,7 +18,7 @@
 //                           stay in registers and are added in CSR order: no float atomics, bitwise
 //                           reproducible sums
 //   graph_node_kernel       the node update per 16-node tile with the segment mean's count.clamp(min=1)
-#include "nonode_common.h"
+#include "nonode_graph_common.h"
 
 namespace {
 
@@ -118,8 +120,7 @@ __global__ __launch_bounds__(256) void graph_proj_kernel(GraphArgs p) {
   f4 hin[4], ap[4], aq[4];
   load_ecl(hin, p.h + (size_t)r * HID, g);
   load_vp(ap, blob + OFF_VEC + V_B1 * 64, g);
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) aq[mt] = f4{0.f, 0.f, 0.f, 0.f};
+  zero4(aq);
   if (__builtin_expect(__any(amax_ecl(hin) > H16_LIMIT), 0)) {
     mfma_dense<4>(ap, blob + OFF_WA, hin, lane);
     mfma_dense<4>(aq, blob + OFF_WB, hin, lane);
@@ -138,98 +139,39 @@ __global__ __launch_bounds__(256) void graph_proj_kernel(GraphArgs p) {
 // The edge walk. W2 / Wc1 fp16 fragments and the edge-phase vectors are staged in LDS once per
 // workgroup (35 KB: four workgroups per CU); every 64x64 product goes through mm64 (fp16x3, or exact
 // f32 MFMAs when the tile's activations leave the fp16 hi range).
+struct SiluInPlace {
+  __device__ __forceinline__ void operator()(f4 (&z)[4], int) const { silu_ecl(z); }
+};
 template <int VARIANT, int KF>
 __global__ __launch_bounds__(256) void graph_edge_kernel(GraphArgs p) {
   __shared__ __attribute__((aligned(16))) float sW[8192 + EDGE_STAGE_FLOATS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, e = lane & 15, g = lane >> 4;
-  for (int i = tid; i < 2048; i += 256) reinterpret_cast<f4*>(sW)[i] = reinterpret_cast<const f4*>(p.blob + OFF_H16)[i];
-  if (tid < EDGE_STAGE_FLOATS / 4)
-    reinterpret_cast<f4*>(sW + 8192)[tid] = reinterpret_cast<const f4*>(p.blob + OFF_FEAT)[tid];
+  stage_edge_weights(sW, sW + 8192, p.blob, tid);
   __syncthreads();
-  const float* sV = sW + 8192;
-  const float* vFEAT = sV;
-  const float* vB2 = sV + 512 + V_B2 * 64;
-  const float* vBC1 = sV + 512 + V_BC1 * 64;
-  const float* vWC2 = sV + 512 + V_WC2 * 64;
-  const h8* w2h = reinterpret_cast<const h8*>(sW);
-  const h8* wc1h = reinterpret_cast<const h8*>(sW + 4096);
-  const float* scal = p.blob + OFF_SCAL;
-  const float bc2 = scal[0];
-  const bool rnorm = scal[SC_NORM] != 0.f, ctanh = scal[SC_TANH] != 0.f;
-  const unsigned us_w2 = h16_us(scal, HS_W2), us_wc1 = h16_us(scal, HS_WC1);
-
-  // frame f owns node rows f n_nodes ..; its tiles never straddle a frame
-  const int tpf = (p.n_nodes + 15) >> 4;
-  const int t = blockIdx.x * 4 + wave;
-  const int f = t / tpf, tile = t - f * tpf;
-  if (f >= p.n_frames) return;
-  const int n = tile * 16 + e;
-  const bool rvalid = n < p.n_nodes;
-  const int nc = rvalid ? n : p.n_nodes - 1;
-  const size_t fbase = (size_t)f * p.n_nodes, r = fbase + nc;
-  const int rp = p.row_ptr[nc];
-  const int deg = rvalid ? p.row_ptr[nc + 1] - rp : 0;
-  int kmax = deg;
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) kmax = max(kmax, __shfl_xor(kmax, o));
-  kmax = __builtin_amdgcn_readfirstlane(kmax);
-  const float* efb = p.ef + (size_t)(f % p.ef_frames) * (size_t)p.E * p.ne;
-  f4 pr[4];
-  load_ecl(pr, p.P + r * HID, g);
-  const float xr0 = p.x[r * 3 + 0], xr1 = p.x[r * 3 + 1], xr2 = p.x[r * 3 + 2];
+  const EdgeWeights w = edge_weights(sW, sW + 8192, p.blob);
+  Tile t;
+  if (!tile_of(p.n_nodes, 0, p.n_frames, e, wave, t)) return;
+  const size_t r = t.r;
+  const CsrRow row(p.row_ptr, t.nc, t.rvalid);
+  EdgeInputs in;
+  in.x = p.x; in.Q = p.Q; in.ne = p.ne;
+  in.efb = p.ef + (size_t)(t.fa % p.ef_frames) * (size_t)p.E * p.ne;
+  load_ecl(in.pr, p.P + r * HID, g);
+  in.xr0 = p.x[r * 3 + 0]; in.xr1 = p.x[r * 3 + 1]; in.xr2 = p.x[r * 3 + 2];
   f4 msum[4];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) msum[mt] = f4{0.f, 0.f, 0.f, 0.f};
+  zero4(msum);
   float fs0 = 0.f, fs1 = 0.f, fs2 = 0.f;
-  // the k-th entry of this column's row; a column past its degree re-reads its first entry (a
-  // receiver without edges: itself and edge 0), so a masked lane computes on finite, in-range data
-  auto entry = [&](int k, int& j, int& id) __attribute__((always_inline)) {
-    if (deg > 0) {
-      const int idx = rp + (k < deg ? k : 0);
-      j = p.col[idx];
-      id = p.eid[idx];
-    } else {
-      j = nc;
-      id = 0;
-    }
-  };
+  SiluInPlace act;
   int jn, idn;
-  entry(0, jn, idn);
+  row.entry(p.col, p.eid, t.nc, 0, jn, idn);
 #pragma unroll 1
-  for (int k = 0; k < kmax; ++k) {
+  for (int k = 0; k < row.kmax; ++k) {
     const int j = jn, id = idn;
-    const bool on = k < deg;
-    entry(k + 1, jn, idn);   // the next step's indices, a step ahead of their gathers
-    const size_t s = fbase + j;
-    const float r0 = xr0 - p.x[s * 3 + 0], r1 = xr1 - p.x[s * 3 + 1], r2 = xr2 - p.x[s * 3 + 2];
-    float d2 = fmaf(r0, r0, fmaf(r1, r1, r2 * r2));
-    if (rnorm) d2 = radial_norm(d2);
-    // pre-activation P_r + Q_s + W1[:, scalars] [|r|^2, e_rs]: the scalar inputs as f32 MFMA k-steps
-    f4 a[4];
-    load_ecl(a, p.Q + s * HID, g);
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) a[mt] += pr[mt];
-#pragma unroll
-    for (int kf = 0; kf < KF; ++kf) {
-      const int fi = 4 * kf + g;
-      float bv = 0.f;
-      if (fi == 0) bv = d2;
-      else if (fi - 1 < p.ne) bv = efb[(size_t)id * p.ne + (fi - 1)];
-      const f4 wf = *reinterpret_cast<const f4*>(vFEAT + kf * 256 + lane * 4);
-#pragma unroll
-      for (int mo = 0; mo < 4; ++mo) a[mo] = mfma(wf[mo], bv, a[mo]);
-    }
-    silu_ecl(a);
-    f4 m[4], c1[4];
-    load_vp(m, vB2, g);
-    mm64(m, w2h, p.blob + OFF_W2, a, lane, us_w2);
-    silu_ecl(m);
-    load_vp(c1, vBC1, g);
-    mm64(c1, wc1h, p.blob + OFF_WC1, m, lane, us_wc1);
-    silu_ecl(c1);
-    float c = dot_vp(c1, vWC2, g) + bc2;
-    if (ctanh) c = tanhf(c);
-    float f0 = r0 * c, f1 = r1 * c, f2 = r2 * c;
+    const bool on = k < row.deg;
+    row.entry(p.col, p.eid, t.nc, k + 1, jn, idn);   // the next step's indices, a step ahead of their gathers
+    EdgeStep st;
+    edge_step<KF>(w, in, t.fbase + j, id, lane, g, act, st);
+    float f0 = st.r0 * st.c, f1 = st.r1 * st.c, f2 = st.r2 * st.c;
     if (VARIANT == SEGNO) {   // gcl.py:99-100 clamps every edge's translation
       f0 = fminf(fmaxf(f0, -100.f), 100.f);
       f1 = fminf(fmaxf(f1, -100.f), 100.f);
@@ -239,14 +181,14 @@ __global__ __launch_bounds__(256) void graph_edge_kernel(GraphArgs p) {
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) msum[mt][q] = on ? msum[mt][q] + m[mt][q] : msum[mt][q];
+      for (int q = 0; q < 4; ++q) msum[mt][q] = on ? msum[mt][q] + st.m[mt][q] : msum[mt][q];
     fs0 = on ? fs0 + f0 : fs0;
     fs1 = on ? fs1 + f1 : fs1;
     fs2 = on ? fs2 + f2 : fs2;
   }
-  if (rvalid) {
+  if (t.rvalid) {
     store_ecl(p.M + r * HID, msum, g);
-    if (g == 0) *reinterpret_cast<f4*>(p.F + r * 4) = f4{fs0, fs1, fs2, (float)deg};
+    if (g == 0) *reinterpret_cast<f4*>(p.F + r * 4) = f4{fs0, fs1, fs2, (float)row.deg};
   }
 }
 
@@ -271,11 +213,9 @@ __global__ __launch_bounds__(256) void graph_node_kernel(GraphArgs p) {
   if (VARIANT == EGNO) {
     // x <- x + phi_v(h) v + clamp(mean_j f_ij, +-100)   (basic.py:174-181)
     f4 t[4];
-    load_vp(t, bj + OFF_VEC + V_BV1 * 64, g);
-    mm64(t, reinterpret_cast<const h8*>(bj + OFF_H16N + H_WV1 * 4096), bj + OFF_WV1, hr, lane,
-         h16_us(bj + OFF_SCAL, HS_N + H_WV1));
+    node_phi_pre(t, bj, hr, lane, g);
     silu_ecl(t);
-    const float phi = dot_vp(t, bj + OFF_VEC + V_WV2 * 64, g) + bj[OFF_SCAL + 1];
+    const float phi = node_phi(t, bj, g);
     nx0 = x0 + phi * v0 + fminf(fmaxf(Fr[0] * inv, -100.f), 100.f);
     nx1 = x1 + phi * v1 + fminf(fmaxf(Fr[1] * inv, -100.f), 100.f);
     nx2 = x2 + phi * v2 + fminf(fmaxf(Fr[2] * inv, -100.f), 100.f);
@@ -290,19 +230,7 @@ __global__ __launch_bounds__(256) void graph_node_kernel(GraphArgs p) {
   }
   // h <- node_mlp([h, sum_j m_ij]) (+ h if recurrent)   (basic.py:182-185, gcl.py:85-95)
   f4 z[4], hn[4];
-  load_vp(z, bj + OFF_VEC + V_BN1 * 64, g);
-  if (__builtin_expect(__any(fmaxf(amax_ecl(hr), amax_ecl(Mr)) > H16_LIMIT), 0)) {
-    f4 in8[8];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) { in8[mt] = hr[mt]; in8[4 + mt] = Mr[mt]; }
-    mfma_dense<8>(z, bj + OFF_WN1, in8, lane);
-  } else {
-    h8 xh[2], xl[2];
-    h16_split(hr, xh, xl);
-    mfma_h16(z, reinterpret_cast<const h8*>(bj + OFF_H16N + H_WN1A * 4096), xh, xl, lane, h16_us(bj + OFF_SCAL, HS_N + H_WN1A));
-    h16_split(Mr, xh, xl);
-    mfma_h16(z, reinterpret_cast<const h8*>(bj + OFF_H16N + H_WN1B * 4096), xh, xl, lane, h16_us(bj + OFF_SCAL, HS_N + H_WN1B));
-  }
+  node_hidden_pre(z, bj, hr, Mr, lane, g);
   silu_ecl(z);
   load_vp(hn, bj + OFF_VEC + V_BN2 * 64, g);
   mm64(hn, reinterpret_cast<const h8*>(bj + OFF_H16N + H_WN2 * 4096), bj + OFF_WN2, z, lane, h16_us(bj + OFF_SCAL, HS_N + H_WN2));

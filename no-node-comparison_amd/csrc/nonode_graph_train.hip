@@ -2,10 +2,10 @@
 // basic.py:167-186, with aggregate basic.py:6-31 and InvariantScalarNet basic.py:107-144): training on
 // gfx950 for the CSR graph kernels of nonode_graph.hip.
 //
-// A translation unit of its own, so the other units compile exactly as before. The forward recompute
-// reads the forward layer blob (nonode_pack_layer: log2-domain SiLU, fp16x3 products with the exact-f32
-// guard of mm64) and so repeats the forward's arithmetic per node and per edge; the transposed
-// products read the backward blob (nonode_pack_layer_bwd: true-scale W^T fp16 hi/lo fragments), every
+// A translation unit of its own (built with the default machine scheduler). The forward recompute
+// calls the forward's own edge step and node pre-activations (nonode_graph_common.h, on the forward
+// layer blob of nonode_pack_layer), keeping SiLU' where the forward applies SiLU in place; the
+// transposed products read the backward blob (nonode_pack_layer_bwd: true-scale W^T fp16 hi/lo fragments), every
 // gradient column scaled by a power of two into [2^11, 2^12) before the fp16 split.
 //
 //   graph_node_bwd_kernel  per 16-node tile: h' = node_mlp([h, M]) and x' = x + phi_v(h) v +
@@ -23,7 +23,7 @@
 //   graph_zero_dropped_kernel  zero rows of edge_ops for edges the CSR build dropped
 // No float atomics: the input gradients are bitwise reproducible and, for a list without duplicate
 // edges, independent of the list's order.
-#include "nonode_bwd_common.h"
+#include "nonode_graph_common.h"
 
 namespace {
 
@@ -57,58 +57,23 @@ __device__ __forceinline__ void silu2_keep(const f4 (&zp)[4], f4 (&a)[4], f4 (&d
   for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(zp[mt][q]));
-      a[mt][q] = zp[mt][q] * s;
-      d[mt][q] = s * fmaf(zp[mt][q] * NEG_LN2, 1.f - s, 1.f);
+      const float z = zp[mt][q];   // a may be zp
+      const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z));
+      a[mt][q] = z * s;
+      d[mt][q] = s * fmaf(z * NEG_LN2, 1.f - s, 1.f);
     }
 }
-// out += W x for a gradient column set x (nonode_train.hip mm64_cs): each column scaled to [2^11, 2^12)
-// before the split, the product scaled back
-__device__ __forceinline__ void mm64_cs(f4 (&out)[4], const h8* wh, const f4 (&x)[4], int lane, unsigned us) {
-  const float sc = p2scale(col_max(amax16(x)));
-  const float inv = 1.f / sc;   // exact (power of two)
-  f4 xs[4], acc[4];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) { xs[mt] = x[mt] * sc; acc[mt] = f4{0.f, 0.f, 0.f, 0.f}; }
-  h8 xh[2], xl[2];
-  h16_split(xs, xh, xl);
-  mfma_h16(acc, wh, xh, xl, lane, us);
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) out[mt] += acc[mt] * inv;
-}
-__device__ __forceinline__ void scale4(f4 (&d)[4], const f4 (&a)[4], float s) {
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) d[mt] = a[mt] * s;
-}
-__device__ __forceinline__ void mul4(f4 (&g)[4], const f4 (&d)[4]) {
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) g[mt] *= d[mt];
-}
-
-// the launch's tile of this wave: frame fr (relative), nodes tile * 16 ..
-struct Tile {
-  int fr, nc;
-  bool rvalid;
-  size_t r, rr;   // node row in the layer's arrays / in node_ops
+// the edge step's activation for the reverse pass: d[i] = SiLU' of pre-activation i
+struct SiluKeep {
+  f4 d[3][4];
+  __device__ __forceinline__ void operator()(f4 (&z)[4], int i) { silu2_keep(z, z, d[i]); }
 };
-__device__ __forceinline__ bool tile_of(const GraphBwdArgs& p, int e, int wave, Tile& t) {
-  const int tpf = (p.n_nodes + 15) >> 4;
-  const int w = blockIdx.x * 4 + wave;
-  t.fr = w / tpf;
-  if (t.fr >= p.nf) return false;
-  const int n = (w - t.fr * tpf) * 16 + e;
-  t.rvalid = n < p.n_nodes;
-  t.nc = t.rvalid ? n : p.n_nodes - 1;
-  t.r = (size_t)(p.f0 + t.fr) * p.n_nodes + t.nc;
-  t.rr = (size_t)t.fr * p.n_nodes + t.nc;
-  return true;
-}
 
 // ---- node reverse (basic.py:174-185 reversed; the per-node count of aggregate, basic.py:28) ---------
 __global__ __launch_bounds__(256) void graph_node_bwd_kernel(GraphBwdArgs p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, e = lane & 15, g = lane >> 4;
   Tile t;
-  if (!tile_of(p, e, wave, t)) return;
+  if (!tile_of(p.n_nodes, p.f0, p.nf, e, wave, t)) return;
   const size_t r = t.r;
   const float* bj = p.blob;
   const float* bb = p.bb;
@@ -118,27 +83,13 @@ __global__ __launch_bounds__(256) void graph_node_bwd_kernel(GraphBwdArgs p) {
   load_ecl(Mr, p.M + r * HID, g);
   const f4 Fr = *reinterpret_cast<const f4*>(p.F + r * 4);
   const float inv = 1.f / fmaxf(Fr[3], 1.f);
-  // forward recompute, as graph_node_kernel: phi_v(h) and the node MLP's hidden layer
+  // forward recompute: phi_v(h) and the node MLP's hidden layer
   f4 tp[4], tt[4], dt[4];
-  load_vp(tp, bj + OFF_VEC + V_BV1 * 64, g);
-  mm64(tp, reinterpret_cast<const h8*>(bj + OFF_H16N + H_WV1 * 4096), bj + OFF_WV1, hr, lane,
-       h16_us(bj + OFF_SCAL, HS_N + H_WV1));
+  node_phi_pre(tp, bj, hr, lane, g);
   silu2_keep(tp, tt, dt);
-  const float phi = dot_vp(tt, bj + OFF_VEC + V_WV2 * 64, g) + bj[OFF_SCAL + 1];
+  const float phi = node_phi(tt, bj, g);
   f4 zp[4], z[4], dz[4];
-  load_vp(zp, bj + OFF_VEC + V_BN1 * 64, g);
-  if (__builtin_expect(__any(fmaxf(amax_ecl(hr), amax_ecl(Mr)) > H16_LIMIT), 0)) {
-    f4 in8[8];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) { in8[mt] = hr[mt]; in8[4 + mt] = Mr[mt]; }
-    mfma_dense<8>(zp, bj + OFF_WN1, in8, lane);
-  } else {
-    h8 xh[2], xl[2];
-    h16_split(hr, xh, xl);
-    mfma_h16(zp, reinterpret_cast<const h8*>(bj + OFF_H16N + H_WN1A * 4096), xh, xl, lane, h16_us(bj + OFF_SCAL, HS_N + H_WN1A));
-    h16_split(Mr, xh, xl);
-    mfma_h16(zp, reinterpret_cast<const h8*>(bj + OFF_H16N + H_WN1B * 4096), xh, xl, lane, h16_us(bj + OFF_SCAL, HS_N + H_WN1B));
-  }
+  node_hidden_pre(zp, bj, hr, Mr, lane, g);
   silu2_keep(zp, z, dz);
   float gx0 = 0.f, gx1 = 0.f, gx2 = 0.f, gv0 = 0.f, gv1 = 0.f, gv2 = 0.f;
   if (p.gxo) { gx0 = p.gxo[r * 3 + 0]; gx1 = p.gxo[r * 3 + 1]; gx2 = p.gxo[r * 3 + 2]; }
@@ -197,100 +148,49 @@ template <int KF>
 __global__ __launch_bounds__(256) void graph_edge_bwd_kernel(GraphBwdArgs p) {
   extern __shared__ __attribute__((aligned(16))) float sW[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, e = lane & 15, g = lane >> 4;
-  for (int i = tid; i < 2048; i += 256) {
-    reinterpret_cast<f4*>(sW)[i] = reinterpret_cast<const f4*>(p.blob + OFF_H16)[i];
+  stage_edge_weights(sW, sW + GEB_VEC, p.blob, tid);
+  for (int i = tid; i < 2048; i += 256)
     reinterpret_cast<f4*>(sW + 8192)[i] = reinterpret_cast<const f4*>(p.bb + BOFF_H16 + BH_W2T * 4096)[i];
-  }
-  if (tid < EDGE_STAGE_FLOATS / 4)
-    reinterpret_cast<f4*>(sW + GEB_VEC)[tid] = reinterpret_cast<const f4*>(p.blob + OFF_FEAT)[tid];
   if (tid < 16) reinterpret_cast<f4*>(sW + GEB_WC2T)[tid] = reinterpret_cast<const f4*>(p.bb + BOFF_VEC + BV_WC2 * 64)[tid];
   else if (tid < 32) reinterpret_cast<f4*>(sW + GEB_WS)[tid - 16] = reinterpret_cast<const f4*>(p.bb + BOFF_VEC + BV_WS * 64)[tid - 16];
   __syncthreads();
   static_assert(BH_WC1T == BH_W2T + 1, "W2^T | Wc1^T are staged as one block");
-  const float* sV = sW + GEB_VEC;
-  const float* vFEAT = sV;
-  const float* vB2 = sV + 512 + V_B2 * 64;
-  const float* vBC1 = sV + 512 + V_BC1 * 64;
-  const float* vWC2 = sV + 512 + V_WC2 * 64;
-  const h8* w2h = reinterpret_cast<const h8*>(sW);
-  const h8* wc1h = reinterpret_cast<const h8*>(sW + 4096);
+  const EdgeWeights w = edge_weights(sW, sW + GEB_VEC, p.blob);
   const h8* w2th = reinterpret_cast<const h8*>(sW + 8192);
   const h8* wc1th = reinterpret_cast<const h8*>(sW + 12288);
-  const float* scal = p.blob + OFF_SCAL;
-  const float bc2 = scal[0];
-  const bool rnorm = scal[SC_NORM] != 0.f, ctanh = scal[SC_TANH] != 0.f;
-  const unsigned us_w2 = h16_us(scal, HS_W2), us_wc1 = h16_us(scal, HS_WC1);
   const unsigned us_w2t = h16_us(p.bb + BOFF_SCAL, BH_W2T), us_wc1t = h16_us(p.bb + BOFF_SCAL, BH_WC1T);
 
   Tile t;
-  if (!tile_of(p, e, wave, t)) return;
-  const int nc = t.nc;
-  const size_t fbase = (size_t)(p.f0 + t.fr) * p.n_nodes, r = t.r;
-  const int rp = p.row_ptr[nc];
-  const int deg = t.rvalid ? p.row_ptr[nc + 1] - rp : 0;
-  int kmax = deg;
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) kmax = max(kmax, __shfl_xor(kmax, o));
-  kmax = __builtin_amdgcn_readfirstlane(kmax);
-  const float* efb = p.ef + (size_t)((p.f0 + t.fr) % p.ef_frames) * (size_t)p.E * p.ne;
+  if (!tile_of(p.n_nodes, p.f0, p.nf, e, wave, t)) return;
+  const size_t r = t.r;
+  const CsrRow row(p.row_ptr, t.nc, t.rvalid);
+  EdgeInputs in;
+  in.x = p.x; in.Q = p.Q; in.ne = p.ne;
+  in.efb = p.ef + (size_t)(t.fa % p.ef_frames) * (size_t)p.E * p.ne;
   float* erow0 = p.eops + (size_t)t.fr * (size_t)p.E * GE_STRIDE;
   const float* nrow = p.nops + t.rr * GN_STRIDE;
-  f4 pr[4], gM[4], GA[4];
-  load_ecl(pr, p.P + r * HID, g);
+  f4 gM[4], GA[4];
+  load_ecl(in.pr, p.P + r * HID, g);
   load_ecl(gM, nrow + GN_GM, g);
   const f4 gF = *reinterpret_cast<const f4*>(nrow + GN_GF);
-  const float xr0 = p.x[r * 3 + 0], xr1 = p.x[r * 3 + 1], xr2 = p.x[r * 3 + 2];
+  in.xr0 = p.x[r * 3 + 0]; in.xr1 = p.x[r * 3 + 1]; in.xr2 = p.x[r * 3 + 2];
   zero4(GA);
   float gxa0 = 0.f, gxa1 = 0.f, gxa2 = 0.f;
-  // the k-th entry of this column's row (graph_edge_kernel's entry: a column past its degree re-reads
-  // its first entry, a receiver without edges itself and edge 0, so a masked lane stays in range)
-  auto entry = [&](int k, int& j, int& id) __attribute__((always_inline)) {
-    if (deg > 0) {
-      const int idx = rp + (k < deg ? k : 0);
-      j = p.col[idx];
-      id = p.eid[idx];
-    } else {
-      j = nc;
-      id = 0;
-    }
-  };
   int jn, idn;
-  entry(0, jn, idn);
+  row.entry(p.col, p.eid, t.nc, 0, jn, idn);
 #pragma unroll 1
-  for (int k = 0; k < kmax; ++k) {
+  for (int k = 0; k < row.kmax; ++k) {
     const int j = jn, id = idn;
-    const bool on = k < deg;
-    entry(k + 1, jn, idn);
-    const size_t s = fbase + j;
-    const float r0 = xr0 - p.x[s * 3 + 0], r1 = xr1 - p.x[s * 3 + 1], r2 = xr2 - p.x[s * 3 + 2];
-    const float d2raw = fmaf(r0, r0, fmaf(r1, r1, r2 * r2));
-    const float d2 = rnorm ? radial_norm(d2raw) : d2raw;
-    // ---- forward recompute (graph_edge_kernel), the sigmoids kept as SiLU' ----
-    f4 z1[4], a[4], d1[4];
-    load_ecl(z1, p.Q + s * HID, g);
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) z1[mt] += pr[mt];
-#pragma unroll
-    for (int kf = 0; kf < KF; ++kf) {
-      const int fi = 4 * kf + g;
-      float bv = 0.f;
-      if (fi == 0) bv = d2;
-      else if (fi - 1 < p.ne) bv = efb[(size_t)id * p.ne + (fi - 1)];
-      const f4 wf = *reinterpret_cast<const f4*>(vFEAT + kf * 256 + lane * 4);
-#pragma unroll
-      for (int mo = 0; mo < 4; ++mo) z1[mo] = mfma(wf[mo], bv, z1[mo]);
-    }
-    silu2_keep(z1, a, d1);
-    f4 z2[4], m[4], dm[4];
-    load_vp(z2, vB2, g);
-    mm64(z2, w2h, p.blob + OFF_W2, a, lane, us_w2);
-    silu2_keep(z2, m, dm);
-    f4 z3[4], c1[4], dc[4];
-    load_vp(z3, vBC1, g);
-    mm64(z3, wc1h, p.blob + OFF_WC1, m, lane, us_wc1);
-    silu2_keep(z3, c1, dc);
-    float c = dot_vp(c1, vWC2, g) + bc2;
-    if (ctanh) c = tanhf(c);
+    const bool on = k < row.deg;
+    row.entry(p.col, p.eid, t.nc, k + 1, jn, idn);
+    // ---- forward recompute, the sigmoids kept as SiLU' ----
+    SiluKeep act;
+    EdgeStep st;
+    edge_step<KF>(w, in, t.fbase + j, id, lane, g, act, st);
+    const f4 (&a)[4] = st.a, (&m)[4] = st.m, (&c1)[4] = st.c1;
+    const f4 (&d1)[4] = act.d[0], (&dm)[4] = act.d[1], (&dc)[4] = act.d[2];
+    const float r0 = st.r0, r1 = st.r1, r2 = st.r2, d2raw = st.d2raw, d2 = st.d2, c = st.c;
+    const bool rnorm = w.rnorm, ctanh = w.ctanh;
     // ---- reverse ----
     float gc = gF[0] * r0 + gF[1] * r1 + gF[2] * r2;   // f_ij = r c, F_i = sum_j f_ij
     if (ctanh) gc *= 1.f - c * c;
@@ -336,7 +236,7 @@ __global__ __launch_bounds__(256) void graph_edge_bwd_kernel(GraphBwdArgs p) {
         float ev[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          if (q < p.ne) ev[q] = efb[(size_t)id * p.ne + q];
+          if (q < p.ne) ev[q] = in.efb[(size_t)id * p.ne + q];
         *reinterpret_cast<f4*>(o + GE_X8) = f4{1.f, d2, ev[0], ev[1]};
         *reinterpret_cast<f4*>(o + GE_X8 + 4) = f4{ev[2], ev[3], 0.f, 0.f};
         *reinterpret_cast<f4*>(o + GE_GC) = f4{gc, dr0, dr1, dr2};
@@ -355,23 +255,17 @@ __global__ __launch_bounds__(256) void graph_edge_bwd_kernel(GraphBwdArgs p) {
 __global__ __launch_bounds__(256) void graph_post_kernel(GraphBwdArgs p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, e = lane & 15, g = lane >> 4;
   Tile t;
-  if (!tile_of(p, e, wave, t)) return;
-  const int nc = t.nc;
+  if (!tile_of(p.n_nodes, p.f0, p.nf, e, wave, t)) return;
   const size_t r = t.r;
-  const int sp = p.srow_ptr[nc];
-  const int deg = t.rvalid ? p.srow_ptr[nc + 1] - sp : 0;
-  int kmax = deg;
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) kmax = max(kmax, __shfl_xor(kmax, o));
-  kmax = __builtin_amdgcn_readfirstlane(kmax);
+  const CsrRow row(p.srow_ptr, t.nc, t.rvalid);
   const float* erow0 = p.eops + (size_t)t.fr * (size_t)p.E * GE_STRIDE;
   f4 GB[4];
   zero4(GB);
   float gs0 = 0.f, gs1 = 0.f, gs2 = 0.f;
 #pragma unroll 1
-  for (int k = 0; k < kmax; ++k) {
-    const bool on = k < deg;
-    const int id = deg > 0 ? p.seid[sp + (on ? k : 0)] : 0;   // a masked lane re-reads a row in range
+  for (int k = 0; k < row.kmax; ++k) {
+    const bool on = k < row.deg;
+    const int id = row.edge(p.seid, k);
     const float* o = erow0 + (size_t)id * GE_STRIDE;
     f4 gz1[4];
     load_ecl(gz1, o + GE_GZ1, g);

@@ -8,25 +8,6 @@ namespace {
 
 using nonode_tu::NodeBwdArgs;
 
-// column-scaled fp16x3 split of a 16-column operand (as mm64_cs); returns the inverse scale
-__device__ __forceinline__ float cs_split(const f4 (&x)[4], h8 (&xh)[2], h8 (&xl)[2]) {
-  const float sc = p2scale(col_max(amax16(x)));
-  f4 xs[4];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) xs[mt] = x[mt] * sc;
-  h16_split(xs, xh, xl);
-  return 1.f / sc;   // exact (power of two)
-}
-// out (+)= inv * W x (W: one staged fragment set)
-template <bool ADD>
-__device__ __forceinline__ void mm_node(f4 (&out)[4], const h8* wh, const h8 (&xh)[2], const h8 (&xl)[2],
-                                        float inv, int lane, unsigned us) {
-  f4 acc[4];
-  zero4(acc);
-  mfma_h16(acc, wh, xh, xl, lane, us);
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) out[mt] = ADD ? out[mt] + acc[mt] * inv : acc[mt] * inv;
-}
 // ---- node_bwd_kernel (NodeBwdArgs) ---------------------------------------------------------------
 // Persistent: one workgroup (8 waves, two per SIMD) per CU stages the node-side matrices in LDS once
 // (112 KB) and its waves walk 16-node tiles. (One tile per wave with the fragments read from L2 moved
@@ -74,11 +55,11 @@ __global__ __launch_bounds__(NB_WAVES * 64) void node_bwd_kernel(NodeBwdArgs p) 
   // phi_v(h) = wv2 . SiLU(WV1 h + bv1) + bv2;  node MLP pre-activation zp = WN1 [h, M] + bn1
   f4 tp[4], zp[4];
   load_vp(tp, bb + BOFF_VEC + BV_BV1 * 64, g);
-  mm_node<true>(tp, W(BH_WV1), xh, xl, inv, lane, us(BH_WV1));
+  mm_cs<true>(tp, W(BH_WV1), xh, xl, inv, lane, us(BH_WV1));
   load_vp(zp, bb + BOFF_VEC + BV_BN1 * 64, g);
-  mm_node<true>(zp, W(BH_WN1A), xh, xl, inv, lane, us(BH_WN1A));
+  mm_cs<true>(zp, W(BH_WN1A), xh, xl, inv, lane, us(BH_WN1A));
   inv = cs_split(Mr, xh, xl);
-  mm_node<true>(zp, W(BH_WN1B), xh, xl, inv, lane, us(BH_WN1B));
+  mm_cs<true>(zp, W(BH_WN1B), xh, xl, inv, lane, us(BH_WN1B));
   f4 t[4];
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) t[mt] = tp[mt];
@@ -101,7 +82,7 @@ __global__ __launch_bounds__(NB_WAVES * 64) void node_bwd_kernel(NodeBwdArgs p) 
   mul_dsilu(gt, tp);
   f4 gh[4];
   inv = cs_split(gt, xh, xl);
-  mm_node<false>(gh, W(BH_WV1T), xh, xl, inv, lane, us(BH_WV1T));
+  mm_cs<false>(gh, W(BH_WV1T), xh, xl, inv, lane, us(BH_WV1T));
   // node MLP reverse: gz = WN2^T gho (.) silu'(zp), gh += WN1h^T gz, gM = WN1m^T gz
   f4 z[4];
 #pragma unroll
@@ -110,12 +91,12 @@ __global__ __launch_bounds__(NB_WAVES * 64) void node_bwd_kernel(NodeBwdArgs p) 
   f4 gho[4], gz[4];
   load_ecl(gho, p.gho + (size_t)r * HID, g);
   inv = cs_split(gho, xh, xl);
-  mm_node<false>(gz, W(BH_WN2T), xh, xl, inv, lane, us(BH_WN2T));
+  mm_cs<false>(gz, W(BH_WN2T), xh, xl, inv, lane, us(BH_WN2T));
   mul_dsilu(gz, zp);
   inv = cs_split(gz, xh, xl);
-  mm_node<true>(gh, W(BH_WN1TH), xh, xl, inv, lane, us(BH_WN1TH));
+  mm_cs<true>(gh, W(BH_WN1TH), xh, xl, inv, lane, us(BH_WN1TH));
   f4 gM[4];
-  mm_node<false>(gM, W(BH_WN1TM), xh, xl, inv, lane, us(BH_WN1TM));
+  mm_cs<false>(gM, W(BH_WN1TM), xh, xl, inv, lane, us(BH_WN1TM));
   if (valid) {
     const size_t o = (size_t)r * HID;
     store_ecl(p.ghp + o, gh, g);

@@ -128,21 +128,6 @@ __global__ void pack_bwd_kernel(PackBatch pb) {
   }
 }
 
-// out += W x for a gradient column set x: each column scaled to [2^11, 2^12) before the split, the
-// product scaled back (per lane: lane (e, g) holds column e)
-__device__ __forceinline__ void mm64_cs(f4 (&out)[4], const h8* wh, const f4 (&x)[4], int lane, unsigned us,
-                                        float cm) {
-  const float sc = p2scale(cm);
-  const float inv = 1.f / sc;   // exact (power of two)
-  f4 xs[4], acc[4];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) { xs[mt] = x[mt] * sc; acc[mt] = f4{0.f, 0.f, 0.f, 0.f}; }
-  h8 xh[2], xl[2];
-  h16_split(xs, xh, xl);
-  mfma_h16(acc, wh, xh, xl, lane, us);
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) out[mt] += acc[mt] * inv;
-}
 __device__ __forceinline__ f4 mfma16k16(h4 a, h4 b, f4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
 }

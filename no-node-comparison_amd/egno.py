@@ -13,6 +13,7 @@ from torch import nn
 
 from . import _lib
 from . import graph as _graph
+from ._lib import f32 as _f32
 from .graph import check_full_graph, finish
 
 
@@ -231,39 +232,40 @@ class EGNO(nn.Module):
         return [pre + f"{mlp}.{k}.{wb}" for mlp in (e, c, v, n) for k in (0, 2) for wb in ("weight", "bias")]
 
     def _packed_bwd(self):
-        """Backward fragments (unscaled forward + transposed) per layer, rebuilt like _packed()."""
+        """Backward fragments per layer, rebuilt like _packed(): unscaled forward + transposed
+        (nonode_pack_layers_bwd), or with flat=True the transposed 256-wide fragments
+        (nonode_pack_layer_flat_bwd)."""
         params = _lib.param_list(self, "pack_bwd", lambda: [p for l in self.layers for p in l.parameters()])
         key = tuple((p.data_ptr(), p._version) for p in params)
         if self._bblobs is not None and key == self._bblob_key:
             return self._bblobs
         L = _lib.lib()
-        dev = self.embedding.weight.device
-        bb = torch.empty(self.n_layers, L.nonode_bwd_blob_floats(), dtype=torch.float32, device=dev)
+        floats = L.nonode_flat_bwd_blob_floats() if self.flat else L.nonode_bwd_blob_floats()
+        bb = torch.empty(self.n_layers, floats, dtype=torch.float32, device=self.embedding.weight.device)
         stream = _lib.stream_of(bb)
-        ws = [layer.weight_struct() for layer in self.layers]   # one launch for every layer
-        WP = ctypes.POINTER(_lib.LayerWeights)
-        P = ctypes.c_void_p * self.n_layers
-        _lib.check(L.nonode_pack_layers_bwd((WP * self.n_layers)(*[ctypes.pointer(w) for w in ws]), self.n_layers,
-                                            self._pack_variant(), self.hidden_nf, self.in_edge_nf,
-                                            P(*[bb[i].data_ptr() for i in range(self.n_layers)]), stream))
+        ws = [layer.weight_struct() for layer in self.layers]
+        if self.flat:
+            for i, w in enumerate(ws):
+                _lib.check(L.nonode_pack_layer_flat_bwd(ctypes.byref(w), self.in_edge_nf, bb[i].data_ptr(), stream))
+        else:   # one launch for every layer
+            WP = ctypes.POINTER(_lib.LayerWeights)
+            P = ctypes.c_void_p * self.n_layers
+            _lib.check(L.nonode_pack_layers_bwd((WP * self.n_layers)(*[ctypes.pointer(w) for w in ws]), self.n_layers,
+                                                self._pack_variant(), self.hidden_nf, self.in_edge_nf,
+                                                P(*[bb[i].data_ptr() for i in range(self.n_layers)]), stream))
         self._bblobs, self._bblob_key = bb, key
         return bb
 
-    def _packed_flat_bwd(self):
-        """Transposed 256-wide fragments per flat layer (nonode_pack_layer_flat_bwd), rebuilt like _packed()."""
-        params = _lib.param_list(self, "pack_bwd", lambda: [p for l in self.layers for p in l.parameters()])
-        key = tuple((p.data_ptr(), p._version) for p in params)
-        if self._bblobs is not None and key == self._bblob_key:
-            return self._bblobs
-        L = _lib.lib()
-        bb = torch.empty(self.n_layers, L.nonode_flat_bwd_blob_floats(), dtype=torch.float32,
-                         device=self.embedding.weight.device)
-        stream = _lib.stream_of(bb)
-        for i, layer in enumerate(self.layers):
-            w = layer.weight_struct()
-            _lib.check(L.nonode_pack_layer_flat_bwd(ctypes.byref(w), self.in_edge_nf, bb[i].data_ptr(), stream))
-        self._bblobs, self._bblob_key = bb, key
-        return bb
+    def _check_t_out(self, timesteps_out, n_nodes, device):
+        """timesteps_out [Bt, T] (default: 0 .. T - 1 for one sample), checked against the node count."""
+        T = self.num_timesteps
+        if timesteps_out is None:
+            timesteps_out = torch.arange(T, device=device).unsqueeze(0)
+        if timesteps_out.dim() != 2 or timesteps_out.shape[1] != T:
+            raise ValueError(f"timesteps_out must be [B, {T}], got {tuple(timesteps_out.shape)}")
+        if n_nodes % timesteps_out.shape[0]:
+            raise ValueError("number of nodes must be a multiple of timesteps_out.shape[0] (egno.py:66)")
+        return timesteps_out
 
     def forward(self, x, h, edge_index, edge_fea, v=None, loc_mean=None, timesteps_in=None, timesteps_out=None):
         """egno.py:37-111. x, v, loc_mean: [BN, 3]; h: [BN, in_node_nf]; edge_index: 2 x [E]
@@ -296,15 +298,8 @@ class EGNO(nn.Module):
         if self.num_inputs > 1:
             return self._forward_multi(x, h, edge_index, edge_fea, v, loc_mean, timesteps_in, timesteps_out)
         _lib.require_device(x, h, v, loc_mean, edge_fea, self.embedding.weight)
-        T = self.num_timesteps
         BN = h.shape[0]
-        if timesteps_out is None:
-            timesteps_out = torch.arange(T, device=x.device).unsqueeze(0)
-        if timesteps_out.dim() != 2 or timesteps_out.shape[1] != T:
-            raise ValueError(f"timesteps_out must be [B, {T}], got {tuple(timesteps_out.shape)}")
-        Bt = timesteps_out.shape[0]
-        if BN % Bt:
-            raise ValueError("number of nodes must be a multiple of timesteps_out.shape[0] (egno.py:66)")
+        timesteps_out = self._check_t_out(timesteps_out, BN, x.device)
         B, N = check_full_graph(edge_index, BN)
         if edge_fea.shape != (B * N * (N - 1), self.in_edge_nf):
             raise ValueError(f"edge_fea must be [{B * N * (N - 1)}, {self.in_edge_nf}], got {tuple(edge_fea.shape)}")
@@ -344,14 +339,8 @@ class EGNO(nn.Module):
         _lib.require_device(x, h, v, loc_mean, edge_fea, timesteps_in if multi else None, self.embedding.weight)
         n = h.shape[-2]
         E = _graph._split(edge_index)[0].numel()
-        if timesteps_out is None:
-            timesteps_out = torch.arange(T, device=x.device).unsqueeze(0)
-        if timesteps_out.dim() != 2 or timesteps_out.shape[1] != T:
-            raise ValueError(f"timesteps_out must be [B, {T}], got {tuple(timesteps_out.shape)}")
+        timesteps_out = self._check_t_out(timesteps_out, n, x.device)
         Bt = timesteps_out.shape[0]
-        if n % Bt:
-            raise ValueError("number of nodes must be a multiple of timesteps_out.shape[0] (egno.py:66)")
-        f32 = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()  # noqa: E731
         t_in = None
         if multi:
             if x.dim() != 3 or x.shape[0] != I or h.dim() != 3 or h.shape[0] != I:
@@ -361,26 +350,22 @@ class EGNO(nn.Module):
             if edge_fea.shape != (I, E, self.in_edge_nf):
                 raise ValueError(f"edge_fea must be [{I}, {E}, {self.in_edge_nf}], got {tuple(edge_fea.shape)}")
             fidx = torch.tensor(self.frame_inputs(T), device=x.device)
-            per_frame = lambda t: None if t is None else f32(t)[fidx].reshape(T * t.shape[1], t.shape[2]).contiguous()  # noqa: E731,E501
+            per_frame = lambda t: None if t is None else _f32(t)[fidx].reshape(T * t.shape[1], t.shape[2]).contiguous()  # noqa: E731,E501
             x, h, v, lm, ef = (per_frame(t) for t in (x, h, v, loc_mean, edge_fea))
-            t_in = f32(timesteps_in)[:, fidx].contiguous()
-            tt = f32(timesteps_out)
+            t_in = _f32(timesteps_in)[:, fidx].contiguous()
+            tt = _f32(timesteps_out)
         else:
             if edge_fea.shape != (E, self.in_edge_nf):
                 raise ValueError(f"edge_fea must be [{E}, {self.in_edge_nf}], got {tuple(edge_fea.shape)}")
-            x, h, v, lm, ef = f32(x), f32(h), f32(v), f32(loc_mean), f32(edge_fea)
+            x, h, v, lm, ef = _f32(x), _f32(h), _f32(v), _f32(loc_mean), _f32(edge_fea)
             tt = self._t_out_f32(timesteps_out)
         row_ptr, col, eid = _graph.csr(edge_index, n, device=x.device)
         blobs, tblobs = self._packed()
-        dev = x.device
-        x_out = torch.empty(T * n, 3, device=dev)
-        v_out = torch.empty(T * n, 3, device=dev)
-        h_out = torch.empty(T * n, self.hidden_nf, device=dev)
         L = _lib.lib()
         ws_bytes = L.nonode_egno_graph_workspace_bytes(n, T, Bt)
-        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev)
+        x_out, v_out, h_out, ws = _lib.alloc_outputs(T * n, self.hidden_nf, ws_bytes, x.device)
         blob_p, (tcw_p, tcx_p, _keep) = self._launch_arrays(blobs, tblobs)
-        ew, eb = f32(self.embedding.weight), f32(self.embedding.bias)
+        ew, eb = _f32(self.embedding.weight), _f32(self.embedding.bias)
         _lib.check(L.nonode_egno_forward_graph(
             n, E, T, self.n_layers, self.in_node_nf, self.in_edge_nf, self.time_emb_dim, self.num_modes, Bt,
             _lib.ptr(x), _lib.ptr(h), _lib.ptr(v), _lib.ptr(lm), _lib.ptr(ef), _lib.ptr(t_in), _lib.ptr(tt),
@@ -391,15 +376,9 @@ class EGNO(nn.Module):
     def _forward_graph_train(self, x, h, edge_index, edge_fea, v, loc_mean, timesteps_out):
         """egno.py:37-111 on any edge list, on the autograd tape (graph="trainable", num_inputs == 1):
         autograd.egno_graph_train. Shapes as _forward_graph's single-input form."""
-        T = self.num_timesteps
         n = h.shape[-2]
         E = _graph._split(edge_index)[0].numel()
-        if timesteps_out is None:
-            timesteps_out = torch.arange(T, device=x.device).unsqueeze(0)
-        if timesteps_out.dim() != 2 or timesteps_out.shape[1] != T:
-            raise ValueError(f"timesteps_out must be [B, {T}], got {tuple(timesteps_out.shape)}")
-        if n % timesteps_out.shape[0]:
-            raise ValueError("number of nodes must be a multiple of timesteps_out.shape[0] (egno.py:66)")
+        timesteps_out = self._check_t_out(timesteps_out, n, x.device)
         if edge_fea.shape != (E, self.in_edge_nf):
             raise ValueError(f"edge_fea must be [{E}, {self.in_edge_nf}], got {tuple(edge_fea.shape)}")
         from .autograd import egno_graph_train
@@ -446,12 +425,11 @@ class EGNO(nn.Module):
         if edge_fea.dim() != 3 or edge_fea.shape != (I, E, self.in_edge_nf):
             raise ValueError(f"edge_fea must be [{I}, {E}, {self.in_edge_nf}], got {tuple(edge_fea.shape)}")
         fidx = torch.tensor(self.frame_inputs(T), device=x.device)
-        f32 = lambda t: t.detach().to(torch.float32)  # noqa: E731
-        per_frame = lambda t: None if t is None else f32(t)[fidx].reshape(T * t.shape[1], t.shape[2]).contiguous()  # noqa: E731,E501
+        per_frame = lambda t: None if t is None else _f32(t)[fidx].reshape(T * t.shape[1], t.shape[2]).contiguous()  # noqa: E731,E501
         with torch.no_grad():
             xf, hf, vf, lmf, eff = (per_frame(t) for t in (x, h, v, loc_mean, edge_fea))
-            t_in = f32(timesteps_in)[:, fidx].contiguous()
-            t_out = f32(timesteps_out).contiguous()
+            t_in = _f32(timesteps_in)[:, fidx].contiguous()
+            t_out = _f32(timesteps_out)
         if self._tapes(x, h, v, loc_mean):
             # the tape's inputs are the caller's per-slot tensors (their gradients: the frames of a slot
             # summed by the kernels); the kernels read the per-frame copies
@@ -477,8 +455,7 @@ class EGNO(nn.Module):
 
     @torch.no_grad()
     def _forward_kernels(self, x, h, edge_fea, v, loc_mean, t_out, B, N):
-        f32 = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()  # noqa: E731
-        x, h, v, lm, ef = f32(x), f32(h), f32(v), f32(loc_mean), f32(edge_fea)
+        x, h, v, lm, ef = _f32(x), _f32(h), _f32(v), _f32(loc_mean), _f32(edge_fea)
         if self.flat:   # nonode_egno_forward_flat: t_in NULL = the single-input embedding
             return self._launch_forward(_lib.lib().nonode_egno_forward_flat, B, N, x, h, v, lm, ef,
                                         self._t_out_f32(t_out), t_in=False)
@@ -488,18 +465,12 @@ class EGNO(nn.Module):
         """nonode_egno_forward (single input) or nonode_egno_forward_frames (t_in given)."""
         T = self.num_timesteps
         blobs, tblobs = self._packed()
-        dev = x.device
-        n = T * B * N
-        x_out = torch.empty(n, 3, device=dev)
-        v_out = torch.empty(n, 3, device=dev)
-        h_out = torch.empty(n, self.hidden_nf, device=dev)
         L = _lib.lib()
         ws_bytes = (L.nonode_egno_flat_workspace_bytes if self.flat else L.nonode_egno_workspace_bytes)(
             B, N, T, tt.shape[0])
-        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev)
+        x_out, v_out, h_out, ws = _lib.alloc_outputs(T * B * N, self.hidden_nf, ws_bytes, x.device)
         blob_p, (tcw_p, tcx_p, _keep) = self._launch_arrays(blobs, tblobs)
-        f32 = lambda t: t if t.dtype == torch.float32 and t.is_contiguous() else t.detach().to(torch.float32).contiguous()  # noqa: E731,E501
-        ew, eb = f32(self.embedding.weight), f32(self.embedding.bias)
+        ew, eb = _f32(self.embedding.weight), _f32(self.embedding.bias)
         tail = (_lib.ptr(ew), _lib.ptr(eb), blob_p, tcw_p, tcx_p, _lib.ptr(x_out), _lib.ptr(v_out),
                 _lib.ptr(h_out), _lib.ptr(ws), ws_bytes, _lib.stream_of(x))
         head = (B, N, T, self.n_layers, self.in_node_nf, self.in_edge_nf, self.time_emb_dim, self.num_modes,

@@ -280,17 +280,14 @@ class SEGNO(nn.Module):
         E = _graph._split(edges)[0].numel()
         if edge_attr.shape != (E, self.in_edge_nf):
             raise ValueError(f"edge_attr must be [{E}, {self.in_edge_nf}]")
-        f32 = lambda t: t.detach().to(torch.float32).contiguous() if t is not None else None  # noqa: E731
+        f32 = _lib.f32
         x, v, ea, his, h_in = f32(x), f32(v), f32(edge_attr), f32(his), f32(h_in)
         dev = x.device
         row_ptr, col, eid = _graph.csr(edges, n, device=dev)
         blob = self._packed()
-        x_out = torch.empty(n, 3, device=dev)
-        v_out = torch.empty(n, 3, device=dev)
-        h_out = torch.empty(n, self.hidden_nf, device=dev)
         L = _lib.lib()
         ws_bytes = L.nonode_segno_graph_workspace_bytes(n)
-        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev)
+        x_out, v_out, h_out, ws = _lib.alloc_outputs(n, self.hidden_nf, ws_bytes, dev)
         ew, eb = f32(self.embedding.weight), f32(self.embedding.bias)
         _lib.check(L.nonode_segno_forward_step_graph(
             n, E, T, self.in_node_nf, self.in_edge_nf, _lib.ptr(his), _lib.ptr(h_in), _lib.ptr(x), _lib.ptr(v),
@@ -308,17 +305,14 @@ class SEGNO(nn.Module):
         B, N = check_full_graph(edges, BN)
         if edge_attr.shape != (B * N * (N - 1), self.in_edge_nf):
             raise ValueError(f"edge_attr must be [{B * N * (N - 1)}, {self.in_edge_nf}]")
-        f32 = lambda t: t.detach().to(torch.float32).contiguous() if t is not None else None  # noqa: E731
+        f32 = _lib.f32
         x, v, ea = f32(x), f32(v), f32(edge_attr)
         his, h_in = f32(his), f32(h_in)
         dev = x.device
         blob = self._packed()
-        x_out = torch.empty(BN, 3, device=dev)
-        v_out = torch.empty(BN, 3, device=dev)
-        h_out = torch.empty(BN, self.hidden_nf, device=dev)
         L = _lib.lib()
         ws_bytes = L.nonode_segno_workspace_bytes(B, N)
-        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev)
+        x_out, v_out, h_out, ws = _lib.alloc_outputs(BN, self.hidden_nf, ws_bytes, dev)
         ew, eb = f32(self.embedding.weight), f32(self.embedding.bias)
         _lib.check(L.nonode_segno_forward_step(
             B, N, T, self.in_node_nf, self.in_edge_nf, _lib.ptr(his), _lib.ptr(h_in), _lib.ptr(x), _lib.ptr(v),
