@@ -190,8 +190,10 @@ __global__ void pack_kernel(PackBatch pb) {
 #define NONODE_STAMP 0
 #endif
 #if NONODE_STAMP
-__device__ unsigned long long g_stamp[16];
-#define STAMP_DECL unsigned long long st_acc[16] = {}, st_last = __builtin_amdgcn_s_memtime();
+#define NONODE_NSTAMP 24   // 0-14: the sections; 16-19: the tile-segment boundary taken apart (tools/stamp_run.py)
+__device__ unsigned long long g_stamp[NONODE_NSTAMP];
+// (32-bit accumulators: a launch is ~5e5 cycles per wave, and 24 of them stay in SGPRs)
+#define STAMP_DECL unsigned st_acc[NONODE_NSTAMP] = {}; unsigned long long st_last = __builtin_amdgcn_s_memtime();
 // (stamp_here: a constexpr of the enclosing body, so one build can stamp some instances only: the
 // stamped 8-wave SEGNO layer crashes LLVM's register allocator)
 #define STAMP(i)                                                   \
@@ -199,17 +201,20 @@ __device__ unsigned long long g_stamp[16];
     if constexpr (stamp_here) {                                    \
       __builtin_amdgcn_sched_barrier(0);                           \
       const unsigned long long _t = __builtin_amdgcn_s_memtime();  \
-      st_acc[i] += _t - st_last;                                   \
+      st_acc[i] += (unsigned)(_t - st_last);                       \
       st_last = _t;                                                \
       __builtin_amdgcn_sched_barrier(0);                           \
     }                                                              \
   } while (0)
 #define STAMP_FLUSH                                                \
   if (stamp_here && lane == 0)                                     \
-    for (int _i = 0; _i < 16; ++_i) atomicAdd(&g_stamp[_i], st_acc[_i]);
+    for (int _i = 0; _i < NONODE_NSTAMP; ++_i) atomicAdd(&g_stamp[_i], (unsigned long long)st_acc[_i]);
+// every LDS read issued so far has landed (stamp builds only: books the wait where it is placed)
+#define STAMP_LDS_WAIT do { if constexpr (stamp_here) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); } while (0)
 #else
 #define STAMP_DECL
 #define STAMP(i) do {} while (0)
+#define STAMP_LDS_WAIT do {} while (0)
 #define STAMP_FLUSH
 #endif
 
@@ -291,6 +296,9 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
   constexpr bool TRIPLE = PAIR && VARIANT == EGNO;   // three-unit iterations before the pairs
   constexpr bool FSPLIT = TRIPLE && NONODE_FSPLIT != 0;   // first SiLU fused into the fp16x3 split
   constexpr bool HOSTCUT = TRIPLE && NONODE_HOSTCUT != 0;   // the chunk shapes' unit splits come with the launch
+  // the tile-segment boundary's levers (nonode_common.h; EGNO only: SEGNO's four-wave code stays as it is)
+  constexpr bool PREB = TRIPLE && NONODE_PREB != 0;
+  constexpr bool UCUT = TRIPLE && NONODE_UCUT != 0;
   [[maybe_unused]] constexpr bool stamp_here = VARIANT == EGNO && NW == 4 && !OPT;   // (NONODE_STAMP builds)
   constexpr bool rnorm = OPT && VARIANT == EGNO;    // basic.py:140-141
   constexpr bool ctanh = OPT && VARIANT == SEGNO;   // gcl.py:57-59
@@ -480,6 +488,14 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
   STAMP_DECL
   int* cut = s_cut[wave];   // (static LDS of the kernel: one array for every body copy)
   int cut_ctc = -1, cut_vl = -1;
+  // b2 / bc1 / wc2 of the edge phase (four waves: in registers). PREB: read before the barrier that
+  // opens the phase (they depend on nothing a phase computes), else at its start
+  [[maybe_unused]] f4 rB2[4], rBC1[4], rWC2[4];
+  auto load_bias = [&]() __attribute__((always_inline)) {
+    load_vp(rB2, vB2_, g);
+    load_vp(rBC1, vBC1_, g);
+    load_vp(rWC2, vWC2_, g);
+  };
   #pragma unroll 1
   for (int step = 0; step < p.steps; ++step) {
   constexpr bool save = VARIANT == SEGNO && SAVE;   // (LayerArgs::sv_h)
@@ -506,6 +522,7 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
       #pragma unroll 1
       for (int job = wave; job < J; job += NW) proj_job(hI, p.blob, rbase, nend, s0, S, job);
     }
+    if constexpr (PREB) load_bias();
     STAMP(6);
     __syncthreads();
     STAMP(7);
@@ -559,14 +576,20 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
           for (int i = 0; i <= NW; ++i) cut[i] = i < NWB ? (i * U) / NWB : U;
         }
       }
-      const int u1 = cut[wave + 1];
+      int u1 = cut[wave + 1];
       int u = cut[wave];
-      f4 rB2[4], rBC1[4], rWC2[4];
-      if (PAIR) {
-        load_vp(rB2, vB2_, g);
-        load_vp(rBC1, vBC1_, g);
-        load_vp(rWC2, vWC2_, g);
+      // UCUT: the wave's range and the cuts as scalars (they are wave-uniform, but read from LDS the
+      // compiler cannot know it): the walk's integer state and loop counters live in SGPRs
+      [[maybe_unused]] int cu[NW + 1], wv = wave;
+      if constexpr (UCUT) {
+        u = __builtin_amdgcn_readfirstlane(u);
+        u1 = __builtin_amdgcn_readfirstlane(u1);
+        wv = __builtin_amdgcn_readfirstlane(wave);
+#pragma unroll
+        for (int j = 0; j <= NW; ++j) cu[j] = __builtin_amdgcn_readfirstlane(cut[j]);
       }
+      if (PAIR && !PREB) load_bias();
+      STAMP(16);   // (chunk preamble: shape, cuts, bias vectors)
       #pragma unroll 1
       while (u < u1) {
         const int tau = min(u / Nm1, ctc - 1);
@@ -704,6 +727,7 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
               f2 = fminf(fmaxf(f2, -100.f), 100.f);
             }
           };
+          STAMP(17);   // (segment state: integer and lane state, receiver reads issued)
           // W2 / Wc1 fp16 fragments held for the whole tile segment in AGPRs, which the MFMAs read as
           // their A operand directly (no LDS re-read per pair, no accvgpr copies)
           H16Frags rw2, rwc1;
@@ -711,6 +735,8 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
           load_h16frags(rwc1, wc1h, lane);
           pin_agpr(rw2);
           pin_agpr(rwc1);
+          STAMP_LDS_WAIT;
+          STAMP(18);   // (fragment reads, until they have landed)
           // recomputation of one unit with column-scaled fp16x3 products (the guard path)
           auto exact_unit = [&](int k, const float (&ev)[KF], f4 (&m)[4], float& f0, float& f1, float& f2)
               __attribute__((always_inline)) {
@@ -814,6 +840,10 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
               fs0 += (f00 + f10) + f20; fs1 += (f01 + f11) + f21; fs2 += (f02 + f12) + f22;
 #pragma unroll
               for (int kf = 0; kf < KF; ++kf) { e0[kf] = n0[kf]; e1[kf] = n1[kf]; e2[kf] = n2[kf]; }
+#if NONODE_STAMP
+              if (k == k_lo) STAMP(19);   // (a segment's first triple: the wait for its edge features)
+              else
+#endif
               STAMP(4);
             }
           }
@@ -1069,9 +1099,14 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
         const int t0 = tau * Nm1, t1 = t0 + (tau == ctc - 1 ? Ul : Nm1);
         bool solo = true;
 #pragma unroll
-        for (int w = 0; w < NW; ++w)
-          if (w != wave && ((w ^ wave) & 1) == 0 && cut[w] < cut[w + 1] && cut[w] < t1 && cut[w + 1] > t0)
-            solo = false;
+        for (int w = 0; w < NW; ++w) {
+          if constexpr (UCUT) {
+            if (w != wv && ((w ^ wv) & 1) == 0 && cu[w] < cu[w + 1] && cu[w] < t1 && cu[w + 1] > t0) solo = false;
+          } else {
+            if (w != wave && ((w ^ wave) & 1) == 0 && cut[w] < cut[w + 1] && cut[w] < t1 && cut[w + 1] > t0)
+              solo = false;
+          }
+        }
         if (rvalid && hp == 0) {
           const int slot = wave & 1;
           float* mrow = sM + slot * slotM + rl * ROWP;
@@ -1320,6 +1355,7 @@ __device__ __forceinline__ void egnn_layer_body(const LayerArgs& p, int (*s_cut)
         else node_job(std::integral_constant<int, 1>{}, bj, first);
       }
     }
+    if constexpr (PREB) load_bias();   // (the next chunk's, or the next step's first)
     STAMP(12);
     __syncthreads();
     STAMP(13);
@@ -1924,9 +1960,11 @@ int launch_layer(int n_graphs, int N, int ne, int ef_mod, const float* h, const 
   }
   const int s_rows = cg * N;
   const int n_units = (n_graphs + cg - 1) / cg;
-  const int G = n_units < cus ? n_units : cus;
+  int G = n_units < cus ? n_units : cus;
+  const int force_wgs = getenv_int("NONODE_WGS");   // (diagnostic: at most this many workgroups, so one walks several chunks)
+  if (force_wgs > 0 && force_wgs < G) G = force_wgs;
   // substep fusion needs one whole-graph chunk per workgroup; keeping h, v in LDS needs the room
-  const int fuse = steps > 1 && cpg == 1 && n_units <= cus;
+  const int fuse = steps > 1 && cpg == 1 && n_units <= G;
   const int keep = fuse && layer_lds_floats(ct, s_rows, 1) * 4 <= LDS_MAX && !getenv_int("NONODE_NO_KEEP");
   const size_t lds = layer_lds_floats(ct, s_rows, keep) * 4;
   LayerArgs a;
@@ -2533,13 +2571,18 @@ int nonode_debug_edge_switches(void) {
   return (NONODE_WALK2 ? 1 : 0) | (NONODE_TRICOST ? 2 : 0) | (NONODE_FSPLIT ? 4 : 0) | (NONODE_HOSTCUT ? 8 : 0);
 }
 
+// the build's tile-segment boundary levers: bit 0 NONODE_PREB, 1 NONODE_UCUT
+int nonode_debug_boundary_switches(void) {
+  return (NONODE_PREB ? 1 : 0) | (NONODE_UCUT ? 2 : 0);
+}
+
 #if NONODE_STAMP
-// diagnostic builds only: read and clear the accumulated per-section wave cycles
-int nonode_debug_stamps(unsigned long long* out16) {
+// diagnostic builds only: read and clear the accumulated per-section wave cycles (NONODE_NSTAMP = 24 slots)
+int nonode_debug_stamps(unsigned long long* out24) {
   if (hipDeviceSynchronize() != hipSuccess) return fail(NONODE_ELAUNCH, "stamps: sync");
-  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_stamp), 16 * sizeof(unsigned long long)) != hipSuccess)
+  if (hipMemcpyFromSymbol(out24, HIP_SYMBOL(g_stamp), NONODE_NSTAMP * sizeof(unsigned long long)) != hipSuccess)
     return fail(NONODE_ELAUNCH, "stamps: copy");
-  unsigned long long z[16] = {};
+  unsigned long long z[NONODE_NSTAMP] = {};
   if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamp), z, sizeof(z)) != hipSuccess) return fail(NONODE_ELAUNCH, "stamps: clear");
   return NONODE_OK;
 }

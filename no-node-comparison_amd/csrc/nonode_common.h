@@ -527,6 +527,15 @@ __host__ __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : 
 #ifndef NONODE_FSPLIT
 #define NONODE_FSPLIT 0    // first SiLU rounded straight into the fp16x3 split (silu_split): -8 instructions
 #endif                     // per unit, +3.2 us
+// Round 8: the tile-segment boundary of the EGNO four-wave edge phase. Neither lever
+// changes a value or the order of a sum; each builds alone. Measured and removed: the edge-feature loads
+// issued first, the fragments read once per chunk, the per-lane divisions replaced, the wave index as a scalar.
+#ifndef NONODE_PREB
+#define NONODE_PREB 1      // b2 / bc1 / wc2 read before the barrier that opens phase B (-0.75 us)
+#endif
+#ifndef NONODE_UCUT
+#define NONODE_UCUT 1      // the wave's unit range and the cuts as scalars (v_readfirstlane): the walk's state
+#endif                     // and loop counters in SGPRs, no scratch (-2.2 us)
 
 // THE walk of a run of L units of a segment's packed-or-ordinary range (k <= kp_hi), shared by the
 // kernel's loops, the cost model and the host debug entry. TRIPLE (EGNO, four waves): triples while

@@ -26,7 +26,7 @@ qq = q.reshape(-1, 1)
 ea = torch.cat([qq[edges[0]] * qq[edges[1]], ((x[edges[0]] - x[edges[1]]) ** 2).sum(-1, keepdim=True)], 1)
 his = v.norm(dim=-1, keepdim=True)
 L = _lib.lib()
-buf = (ctypes.c_ulonglong * 16)()
+buf = (ctypes.c_ulonglong * 24)()
 calls = 5
 with torch.no_grad():
     model(his, x, edges, v, ea, T=T)

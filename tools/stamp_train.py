@@ -22,7 +22,7 @@ model = pkg.EGNO(n_layers=4, in_node_nf=2, in_edge_nf=2, hidden_nf=64, with_v=Tr
                  num_timesteps=10, time_emb_dim=32, device=dev).train()
 case = bench.build_egno_case(512, 20, 10, seed=1234, dev=dev)
 L = _lib.lib()
-buf = (ctypes.c_ulonglong * 16)()
+buf = (ctypes.c_ulonglong * 24)()
 acc = [0] * 16
 reps = 3
 for it in range(reps + 1):
