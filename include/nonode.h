@@ -649,6 +649,48 @@ int nonode_segno_forward_step_graph(int n_nodes, long long E, int T, int in_node
                                     const int* col, const int* eid, float coords_weight, int recurrent, float* x_out,
                                     float* v_out, float* h_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * ---- neighbour graphs built on the device, featurisation on an explicit list (csrc/nonode_neighbor.hip) ----
+ *
+ * nonode_neighbor_graph stands in for no reference code: the reference builds only full graphs. It is
+ * what a rollout on a k-NN / cut-off graph calls every segment (the drivers harness.egno_rollout_graph /
+ * segno_rollout_graph mirror rollout_fn, main_simulation_simple_no.py:342-384 and train_nbody.py:200-236,
+ * as loops of model segments over these entries).
+ *
+ * The batch is B graphs of N consecutive rows of x [B*N][3]. A candidate of receiver i is a node j != i of
+ * the same graph with d2 <= r2_max true, where d = x_i - x_j componentwise and
+ * d2 = ((d0*d0) + (d1*d1)) + (d2*d2), every operation rounded to f32 on its own (no fused multiply-add;
+ * a NaN distance is never a candidate). Row i keeps the min(k, candidates) smallest candidates under the
+ * total order (d2, j) and lists them by ascending sender: the CSR nonode_graph_build gives the same edge
+ * set. With E = row_ptr[B*N] and cap = B*N*min(k, N-1): for p < E, col[p] = sender and rows[p] = receiver
+ * (global row indices), eid[p] = p; for E <= p < cap, col[p] = rows[p] = -1, eid[p] = p. k in [1, 64];
+ * r2_max > 0, +inf allowed. No float atomics, no launch sized from device data: bitwise reproducible.
+ * Asynchronous. Workspace: nonode_neighbor_graph_workspace_bytes(B, N, k).
+ */
+size_t nonode_neighbor_graph_workspace_bytes(int B, int N, int k);
+int nonode_neighbor_graph(int B, int N, int k, float r2_max, const float* x, int* row_ptr, int* col, int* eid,
+                          int* rows, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The node side of prepare_inputs (main_simulation_simple_no.py:311-339, num_inputs == 1) without its
+ * full-graph edge column: loc, vel [F][B*N][3], frame t_in[b] - 1 of sample b (python index; NULL: the last
+ * frame) -> x_out, v_out [B*N][3], nodes [B*N][1 + (charges != NULL)] = [|v|, q], loc_mean [B*N][3] (the
+ * per-graph mean; NULL: skipped). Any N (nothing is staged per graph).
+ */
+int nonode_prepare_nodes(int B, int N, int F, const float* loc, const float* vel, const int* t_in,
+                         const float* charges, float* x_out, float* v_out, float* nodes, float* loc_mean,
+                         void* stream);
+
+/*
+ * The edge side on an explicit list (the reference computes these columns only in the full order:
+ * main_simulation_simple_no.py:328-338, train_nbody.py:203,229-233): edge_attr[p] = [q_r*q_c, |x_r - x_c|^2]
+ * ([cap][2]), or [|x_r - x_c|^2] ([cap][1]) with charges = NULL, for r = rows[p], c = cols[p] (idx_bytes 4
+ * or 8) and p < *n_edges (a device pointer; NULL: p < cap). Rows at or past the count, and pairs with an
+ * index outside [0, n_nodes), are zero. The distance uses nonode_neighbor_graph's arithmetic.
+ */
+int nonode_edge_features(long long cap, int n_nodes, const void* rows, const void* cols, int idx_bytes,
+                         const int* n_edges, const float* x, const float* charges, float* edge_attr, void* stream);
+
 
 /* ---- rollout metrics ---- */
 

@@ -42,6 +42,7 @@ SYMBOLS = (
     "nonode_segno_graph_workspace_bytes", "nonode_segno_forward_step_graph",
     "nonode_graph_edge_mask", "nonode_egnn_layer_graph_bwd_node_floats", "nonode_egnn_layer_graph_bwd_edge_floats",
     "nonode_egnn_layer_graph_bwd",
+    "nonode_neighbor_graph_workspace_bytes", "nonode_neighbor_graph", "nonode_prepare_nodes", "nonode_edge_features",
 )
 
 VARIANT_EGNO = 0
@@ -253,6 +254,11 @@ def lib():
     L.nonode_egnn_layer_graph_bwd_edge_floats.argtypes = [_i, _ll]
     L.nonode_egnn_layer_graph_bwd_edge_floats.restype = _sz
     L.nonode_egnn_layer_graph_bwd.argtypes = [_i] * 3 + [_ll] + [_i] * 4 + [_vp] * 22
+    L.nonode_neighbor_graph_workspace_bytes.argtypes = [_i] * 3
+    L.nonode_neighbor_graph_workspace_bytes.restype = _sz
+    L.nonode_neighbor_graph.argtypes = [_i, _i, _i, _f] + [_vp] * 6 + [_sz, _vp]
+    L.nonode_prepare_nodes.argtypes = [_i] * 3 + [_vp] * 9
+    L.nonode_edge_features.argtypes = [_ll, _i, _vp, _vp, _i] + [_vp] * 5
     L.nonode_profile_begin.argtypes = [_i]
     L.nonode_profile_end.argtypes = [ctypes.POINTER(_f), ctypes.POINTER(_i), _i]
     for s in SYMBOLS:

@@ -26,6 +26,9 @@ int graph_layer(int variant, int n_frames, int n_nodes, long long E, int ne, int
                 const float* x, const float* v, const float* ef, const float* blob, const int* row_ptr,
                 const int* col, const int* eid, float dt, float cw, int recurrent, float* h_out, float* x_out,
                 float* v_out, float* ws, hipStream_t s);
+// its one-workgroup scan, for the neighbour-graph builder (nonode_neighbor.hip): row_ptr [n + 1] = the
+// exclusive prefix sum of cnt [n], and cnt <- row_ptr[0 .. n)
+int graph_scan(int n, int* cnt, int* row_ptr, hipStream_t s);
 }
 
 namespace {

@@ -271,6 +271,11 @@ namespace nonode_tu {
 
 size_t graph_layer_ws_floats(long long n_total) { return (size_t)n_total * GRAPH_WS_ROW; }
 
+int graph_scan(int n, int* cnt, int* row_ptr, hipStream_t s) {
+  hipLaunchKernelGGL(graph_scan_kernel, dim3(1), dim3(1024), 0, s, n, cnt, row_ptr);
+  return check_launch("graph_scan_kernel");
+}
+
 int graph_layer(int variant, int n_frames, int n_nodes, long long E, int ne, int ef_frames, const float* h,
                 const float* x, const float* v, const float* ef, const float* blob, const int* row_ptr,
                 const int* col, const int* eid, float dt, float cw, int recurrent, float* h_out, float* x_out,

@@ -1,0 +1,282 @@
+// Neighbour graphs built on the device, and featurisation on an explicit edge list: what a rollout on
+// a k-NN / cut-off graph needs every segment (the reference builds only fully connected graphs, so
+// nothing here stands in for reference code but the featurisation's arithmetic,
+// main_simulation_simple_no.py:311-339 / train_nbody.py:222-234, on the pairs a list names).
+//
+// A translation unit of its own (default machine scheduler). Every distance is computed with
+// individually rounded f32 operations, so a numpy restatement gives the same bits and the graph is a
+// pure function of the positions. Floating-point contraction is switched off for the whole unit by the
+// pragma below: HIP's default is -ffp-contract=fast, and this toolchain's __fmul_rn / __fadd_rn are
+// plain * and + inside a header compiled with contraction on, which the backend fuses into v_fmac_f32
+// even here: so the arithmetic below is written with the plain operators, under the pragma
+// (tests/test_gpu_neighbor.py has senders whose unfused distances tie and whose fused ones do not).
+//
+//   neighbor_select_kernel  one wave per receiver: the min(k, candidates) smallest candidates under
+//                           the total order (d2, j), kept sorted across the 64 lanes; the row written
+//                           by ascending sender at a fixed pitch, and its degree
+//   (scan)                  row_ptr = exclusive prefix sum of the degrees (nonode_graph.hip's
+//                           one-workgroup scan)
+//   neighbor_compact_kernel fixed-pitch rows -> CSR (col, rows, eid), and the -1 tail
+//   node_features_kernel    the node side of prepare_inputs (frame choice, |v|, q, per-graph mean)
+//   edge_features_kernel    [q_r q_c, |x_r - x_c|^2] per listed edge below a device-side count
+#include "nonode_common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+typedef unsigned long long u64;
+constexpr u64 KEY_NONE = ~0ull;   // a non-candidate: above every (d2, j) key
+
+__device__ __forceinline__ u64 shfl64(u64 v, int src) {
+  const unsigned lo = (unsigned)__shfl((int)(unsigned)v, src);
+  const unsigned hi = (unsigned)__shfl((int)(unsigned)(v >> 32), src);
+  return ((u64)hi << 32) | lo;
+}
+__device__ __forceinline__ u64 shfl_up64(u64 v) {   // lane l takes lane l - 1's value (lane 0 keeps its own)
+  const unsigned lo = (unsigned)__shfl_up((int)(unsigned)v, 1);
+  const unsigned hi = (unsigned)__shfl_up((int)(unsigned)(v >> 32), 1);
+  return ((u64)hi << 32) | lo;
+}
+// stages j = from, from/2 .. 1 of a bitonic network; the 64-lane block that lane belongs to at size
+// `blk` sorts ascending when (lane & blk) == 0 (blk = 64: all lanes ascending)
+__device__ __forceinline__ u64 bitonic_stages(u64 v, int lane, int blk, int from) {
+  const bool up = (lane & blk) == 0;
+  for (int j = from; j > 0; j >>= 1) {
+    const u64 o = shfl64(v, lane ^ j);
+    const bool lower = (lane & j) == 0;
+    const u64 mn = v < o ? v : o, mx = v < o ? o : v;
+    v = (lower == up) ? mn : mx;
+  }
+  return v;
+}
+// the wave's 64 keys, ascending by lane
+__device__ __forceinline__ u64 bitonic_sort(u64 v, int lane) {
+  for (int blk = 2; blk <= 64; blk <<= 1) v = bitonic_stages(v, lane, blk, blk >> 1);
+  return v;
+}
+
+// d2 = ((d0 d0) + (d1 d1)) + (d2 d2), every operation rounded to f32 on its own
+__device__ __forceinline__ float dist2(float a0, float a1, float a2, float b0, float b1, float b2) {
+  const float d0 = a0 - b0, d1 = a1 - b1, d2 = a2 - b2;
+  return ((d0 * d0) + (d1 * d1)) + (d2 * d2);
+}
+
+// One wave per receiver r = g N + i. Lane l of `best` holds the l-th smallest key seen so far
+// (ascending). Of a chunk of 64 candidates only the keys below the kk-th best matter (that bound only
+// falls, so a key at or above it never reaches the final kk): none, the chunk is skipped; a few
+// (INSERT_MAX), each is inserted at its rank (one ballot, one lane shift); more, the chunk is sorted
+// and merged in. tmp [B N][kk]: the row's senders (global index) ascending; deg [B N].
+constexpr int INSERT_MAX = 8;
+__global__ __launch_bounds__(256) void neighbor_select_kernel(int n_total, int N, int kk, float r2_max,
+                                                              const float* __restrict__ x, int* __restrict__ tmp,
+                                                              int* __restrict__ deg) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n_total) return;   // (wave-uniform)
+  const int g0 = (r / N) * N, i = r - g0;
+  const float xi0 = x[(size_t)r * 3 + 0], xi1 = x[(size_t)r * 3 + 1], xi2 = x[(size_t)r * 3 + 2];
+  u64 best = KEY_NONE;
+  for (int base = 0; base < N; base += 64) {
+    const int j = base + lane;
+    u64 key = KEY_NONE;
+    if (j < N && j != i) {
+      const size_t s = (size_t)(g0 + j) * 3;
+      const float d2 = dist2(xi0, xi1, xi2, x[s + 0], x[s + 1], x[s + 2]);
+      // d2 >= +0 here (a NaN fails the compare), so its bits order as an unsigned integer
+      if (d2 <= r2_max) key = ((u64)__float_as_uint(d2) << 32) | (unsigned)j;
+    }
+    const u64 kth = shfl64(best, kk - 1);
+    u64 below = __ballot(key < kth);
+    if (!below) continue;
+    if (__popcll(below) <= INSERT_MAX) {
+      while (below) {   // (wave-uniform)
+        const u64 nk = shfl64(key, __ffsll((long long)below) - 1);
+        below &= below - 1;
+        const int pos = __popcll(__ballot(best < nk));
+        const u64 up = shfl_up64(best);
+        best = lane < pos ? best : (lane == pos ? nk : up);
+      }
+      continue;
+    }
+    key = bitonic_sort(key, lane);
+    // best ascending, the chunk descending: the lane-wise minimum holds the 64 smallest of the 128
+    // as a bitonic sequence, which one merge pass sorts
+    const u64 rev = shfl64(key, 63 - lane);
+    best = bitonic_stages(best < rev ? best : rev, lane, 64, 32);
+  }
+  const bool kept = lane < kk && best != KEY_NONE;
+  const int d = __popcll(__ballot(kept));
+  // the kept senders by ascending index (the sentinel sorts last)
+  u64 byj = kept ? (u64)(unsigned)best : KEY_NONE;
+  byj = bitonic_sort(byj, lane);
+  if (lane < d) tmp[(size_t)r * kk + lane] = g0 + (int)(unsigned)byj;
+  if (lane == 0) deg[r] = d;
+}
+
+// thread t = r kk + l: entry l of row r moves to row_ptr[r] + l; position t of the outputs, when it is
+// at or past the edge count, gets the tail's (-1, -1, t)
+__global__ __launch_bounds__(256) void neighbor_compact_kernel(long long cap, int n_total, int kk,
+                                                               const int* __restrict__ row_ptr,
+                                                               const int* __restrict__ tmp, int* __restrict__ col,
+                                                               int* __restrict__ eid, int* __restrict__ rows) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= cap) return;
+  const int r = (int)(t / kk), l = (int)(t - (long long)r * kk);
+  const int p0 = row_ptr[r], d = row_ptr[r + 1] - p0;
+  if (l < d) {
+    const int p = p0 + l;
+    col[p] = tmp[t];
+    rows[p] = r;
+    eid[p] = p;
+  }
+  if (t >= row_ptr[n_total]) {
+    col[t] = -1;
+    rows[t] = -1;
+    eid[t] = (int)t;
+  }
+}
+
+// The node side of prepare_inputs, one 256-thread block per graph: frame t_in[b] - 1 (python index;
+// null: the last frame) of loc, vel [F][B N][3] -> x, v [B N][3], nodes = [|v|] or [|v|, q], loc_mean
+// [B N][3]. The mean's sum is a fixed tree (per-thread strided partial sums, then halving in LDS).
+__global__ __launch_bounds__(256) void node_features_kernel(int B, int N, int F, const float* __restrict__ loc,
+                                                            const float* __restrict__ vel, const int* __restrict__ t_in,
+                                                            const float* __restrict__ q, float* __restrict__ x_out,
+                                                            float* __restrict__ v_out, float* __restrict__ nodes,
+                                                            float* __restrict__ loc_mean) {
+  __shared__ float part[3][256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int f = F - 1;
+  if (t_in) f = ((t_in[b] - 1) % F + F) % F;
+  const size_t BN = (size_t)B * N, r0 = (size_t)b * N;
+  const float* lf = loc + ((size_t)f * BN + r0) * 3;
+  const float* vf = vel + ((size_t)f * BN + r0) * 3;
+  const int nn = q ? 2 : 1;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  for (int i = tid; i < N; i += 256) {
+    const size_t r = r0 + i;
+    const float x0 = lf[i * 3 + 0], x1 = lf[i * 3 + 1], x2 = lf[i * 3 + 2];
+    const float v0 = vf[i * 3 + 0], v1 = vf[i * 3 + 1], v2 = vf[i * 3 + 2];
+    x_out[r * 3 + 0] = x0; x_out[r * 3 + 1] = x1; x_out[r * 3 + 2] = x2;
+    v_out[r * 3 + 0] = v0; v_out[r * 3 + 1] = v1; v_out[r * 3 + 2] = v2;
+    nodes[r * nn] = sqrtf(((v0 * v0) + (v1 * v1)) + (v2 * v2));
+    if (q) nodes[r * nn + 1] = q[r];
+    s0 += x0; s1 += x1; s2 += x2;
+  }
+  part[0][tid] = s0; part[1][tid] = s1; part[2][tid] = s2;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) {
+      part[0][tid] += part[0][tid + o];
+      part[1][tid] += part[1][tid + o];
+      part[2][tid] += part[2][tid + o];
+    }
+    __syncthreads();
+  }
+  if (!loc_mean) return;
+  const float m0 = part[0][0] / (float)N, m1 = part[1][0] / (float)N, m2 = part[2][0] / (float)N;
+  for (int i = tid; i < N; i += 256) {
+    const size_t r = r0 + i;
+    loc_mean[r * 3 + 0] = m0; loc_mean[r * 3 + 1] = m1; loc_mean[r * 3 + 2] = m2;
+  }
+}
+
+// edge_attr[p] = [q_r q_c, |x_r - x_c|^2] (without q: the distance alone) for p below the count
+// (*n_edges, or cap when n_edges is null); zero at and past it, and for a pair with an index outside
+// [0, n_nodes) (which the model's CSR build reports)
+template <typename I>
+__global__ __launch_bounds__(256) void edge_features_kernel(long long cap, int n_nodes, const I* __restrict__ rows,
+                                                            const I* __restrict__ cols, const int* __restrict__ n_edges,
+                                                            const float* __restrict__ x, const float* __restrict__ q,
+                                                            float* __restrict__ ea) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= cap) return;
+  const long long n = n_edges ? (long long)*n_edges : cap;
+  float prod = 0.f, d2 = 0.f;
+  if (p < n) {
+    const long long r = (long long)rows[p], c = (long long)cols[p];
+    if (r >= 0 && r < n_nodes && c >= 0 && c < n_nodes) {
+      d2 = dist2(x[r * 3 + 0], x[r * 3 + 1], x[r * 3 + 2], x[c * 3 + 0], x[c * 3 + 1], x[c * 3 + 2]);
+      if (q) prod = q[r] * q[c];
+    }
+  }
+  if (q) {
+    ea[p * 2 + 0] = prod;
+    ea[p * 2 + 1] = d2;
+  } else {
+    ea[p] = d2;
+  }
+}
+
+long long neighbor_capacity(int B, int N, int k) { return (long long)B * N * (k < N - 1 ? k : N - 1); }
+
+}  // namespace
+
+extern "C" {
+
+size_t nonode_neighbor_graph_workspace_bytes(int B, int N, int k) {
+  if (B <= 0 || N <= 0 || k < 1 || k > 64) return 0;
+  // the degrees, the fixed-pitch rows
+  return ((size_t)B * N + (size_t)neighbor_capacity(B, N, k)) * sizeof(int);
+}
+
+int nonode_neighbor_graph(int B, int N, int k, float r2_max, const float* x, int* row_ptr, int* col, int* eid,
+                          int* rows, void* workspace, size_t workspace_bytes, void* stream) {
+  if (B <= 0 || N <= 0 || k < 1 || k > 64 || !(r2_max > 0.f) || (long long)B * N >= (1ll << 30) ||
+      neighbor_capacity(B, N, k) >= (1ll << 31))
+    return fail(NONODE_EINVAL, "neighbor_graph: B=%d N=%d k=%d r2_max=%g (k in [1, 64], r2_max > 0)", B, N, k,
+                (double)r2_max);
+  const long long cap = neighbor_capacity(B, N, k);
+  if (!x || !row_ptr || !workspace || (cap > 0 && (!col || !eid || !rows)))
+    return fail(NONODE_EINVAL, "neighbor_graph: null pointer");
+  if (workspace_bytes < nonode_neighbor_graph_workspace_bytes(B, N, k))
+    return fail(NONODE_EINVAL, "neighbor_graph: workspace %zu < %zu", workspace_bytes,
+                nonode_neighbor_graph_workspace_bytes(B, N, k));
+  hipStream_t s = (hipStream_t)stream;
+  const int n_total = B * N, kk = k < N - 1 ? k : N - 1;
+  int* deg = (int*)workspace;
+  int* tmp = deg + n_total;
+  if (kk == 0) {   // N = 1: no pair at all
+    if (hipMemsetAsync(row_ptr, 0, ((size_t)n_total + 1) * sizeof(int), s) != hipSuccess)
+      return fail(NONODE_ELAUNCH, "neighbor_graph: memset");
+    return NONODE_OK;
+  }
+  hipLaunchKernelGGL(neighbor_select_kernel, dim3((n_total + 3) / 4), dim3(256), 0, s, n_total, N, kk, r2_max, x, tmp,
+                     deg);
+  if (int rc = check_launch("neighbor_select_kernel")) return rc;
+  if (int rc = nonode_tu::graph_scan(n_total, deg, row_ptr, s)) return rc;
+  hipLaunchKernelGGL(neighbor_compact_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, cap, n_total, kk,
+                     row_ptr, tmp, col, eid, rows);
+  return check_launch("neighbor_compact_kernel");
+}
+
+int nonode_prepare_nodes(int B, int N, int F, const float* loc, const float* vel, const int* t_in,
+                         const float* charges, float* x_out, float* v_out, float* nodes, float* loc_mean,
+                         void* stream) {
+  if (B <= 0 || N <= 0 || F <= 0 || (long long)F * B * N >= (1ll << 30))
+    return fail(NONODE_EINVAL, "prepare_nodes: B=%d N=%d F=%d", B, N, F);
+  if (!loc || !vel || !x_out || !v_out || !nodes) return fail(NONODE_EINVAL, "prepare_nodes: null pointer");
+  hipLaunchKernelGGL(node_features_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, B, N, F, loc, vel, t_in,
+                     charges, x_out, v_out, nodes, loc_mean);
+  return check_launch("node_features_kernel");
+}
+
+int nonode_edge_features(long long cap, int n_nodes, const void* rows, const void* cols, int idx_bytes,
+                         const int* n_edges, const float* x, const float* charges, float* edge_attr, void* stream) {
+  if (cap < 0 || cap >= (1ll << 31) || n_nodes <= 0 || (idx_bytes != 4 && idx_bytes != 8))
+    return fail(NONODE_EINVAL, "edge_features: cap=%lld n_nodes=%d idx_bytes=%d", cap, n_nodes, idx_bytes);
+  if (cap == 0) return NONODE_OK;
+  if (!rows || !cols || !x || !edge_attr) return fail(NONODE_EINVAL, "edge_features: null pointer");
+  const unsigned blocks = (unsigned)((cap + 255) / 256);
+  hipStream_t s = (hipStream_t)stream;
+  if (idx_bytes == 8)
+    hipLaunchKernelGGL(edge_features_kernel<long long>, dim3(blocks), dim3(256), 0, s, cap, n_nodes,
+                       (const long long*)rows, (const long long*)cols, n_edges, x, charges, edge_attr);
+  else
+    hipLaunchKernelGGL(edge_features_kernel<int>, dim3(blocks), dim3(256), 0, s, cap, n_nodes, (const int*)rows,
+                       (const int*)cols, n_edges, x, charges, edge_attr);
+  return check_launch("edge_features_kernel");
+}
+
+}  // extern "C"

@@ -24,9 +24,17 @@ host list; for a device list it goes through the same flag / ``finish()`` / defe
 with ``nonode_graph_build`` as the flag's writer (it drops the bad edge, so no kernel reads out of range).
 Training on such a list (``EGNO(graph="trainable")``) also needs the CSR by sender and, for a device list,
 the mask of the edges the build kept (``csr_by_sender``, cached per edge tensor pair as well).
+
+Neighbour graphs (``neighbor_graph``, csrc/nonode_neighbor.hip): the k-NN / cut-off graph of an equal-size
+batch, built on the device from the positions as a ``NeighborGraph``, which carries its own CSR (valid by
+construction: no check, no cache entry) and goes wherever an edge list goes. A rollout rebuilds it every
+segment (harness.egno_rollout_graph / segno_rollout_graph).
 """
+import math
+import operator
 from collections import OrderedDict
 
+import numpy as np
 import torch
 
 # validated edge tensors, keyed by address / version / shape. Each entry holds a reference to its
@@ -74,6 +82,8 @@ def full_edges(B, N, device="cpu"):
 
 
 def _split(edge_index):
+    if isinstance(edge_index, NeighborGraph):
+        return edge_index.rows, edge_index.col
     if isinstance(edge_index, (list, tuple)):
         if len(edge_index) != 2:
             raise ValueError("edge_index must be [rows, cols]")
@@ -232,6 +242,8 @@ def sync_checks(device=None):
 def known_full(edge_index, n_nodes):
     """(B, N) if this very edge tensor pair is already known to be the fully connected list (a hit in
     the cache of check_full_graph, which lists made by full_edges on the device enter), else None."""
+    if isinstance(edge_index, NeighborGraph):
+        return None
     rows, cols = _split(edge_index)
     hit = _checked.get(_key(rows, cols, rows.numel(), n_nodes))
     return None if hit is None else (hit[0], hit[1])
@@ -259,7 +271,13 @@ def csr(edge_index, n_nodes, device=None):
     nonode_graph_build per edge tensor pair (cached like check_full_graph's verdicts). A host list is
     checked on the spot (ValueError) and copied to `device` (default: the current ROCm device); a device
     list with an index outside [0, n_nodes) has that edge dropped, the device flag set (finish() then
-    NaN-fills the forward's outputs) and ValueError raised by a later call or sync_checks()."""
+    NaN-fills the forward's outputs) and ValueError raised by a later call or sync_checks().
+    A NeighborGraph gives its own CSR: no launch, no cache entry (its -1 tail is no edge to check)."""
+    if isinstance(edge_index, NeighborGraph):
+        covered = edge_index.row_ptr.numel() - 1
+        if n_nodes != covered:
+            raise ValueError(f"csr: the NeighborGraph covers {covered} nodes, n_nodes = {n_nodes}")
+        return edge_index.row_ptr, edge_index.col, edge_index.eid
     rows, cols = _split(edge_index)
     check_host_range(edge_index, n_nodes)
     E = rows.numel()
@@ -296,6 +314,88 @@ def csr(edge_index, n_nodes, device=None):
     while len(_csr) > _CACHE:
         _csr.popitem(last=False)
     return row_ptr, col, eid
+
+
+# ---- neighbour graphs built on the device (k-NN / cut-off; csrc/nonode_neighbor.hip) ----
+
+class NeighborGraph:
+    """A k-NN / cut-off graph of B equal-size graphs, built on the device by ``neighbor_graph``: int32
+    device tensors ``row_ptr`` [B N + 1], ``col``, ``rows``, ``eid`` [capacity] (the CSR by receiver,
+    rows ordered by sender, and the receiver of every entry), ``capacity`` = B N min(k, N - 1) (known on
+    the host), ``n_edges`` = ``row_ptr[-1:]`` (the edge count, a one-element device view: reading it
+    synchronises) and ``n_nodes`` = N. Entries at or past the edge count are (-1, -1): the graph kernels
+    read only what the CSR names, so per-edge features for it are [capacity, .] and their tail is never read.
+
+    It behaves as the pair [rows, col] (len 2, indexing, iteration), so it goes wherever an edge list goes:
+    EGNO / SEGNO built with graph="any" (and EGNO(graph="trainable") off the tape), graph.csr (which
+    returns this object's own CSR without a launch)."""
+
+    def __init__(self, rows, col, row_ptr, eid, n_nodes):
+        self.rows, self.col, self.row_ptr, self.eid = rows, col, row_ptr, eid
+        self.capacity = rows.numel()
+        self.n_edges = row_ptr[-1:]
+        self.n_nodes = n_nodes
+
+    def __len__(self):
+        return 2
+
+    def __getitem__(self, i):
+        return (self.rows, self.col)[i]
+
+    def __iter__(self):
+        return iter((self.rows, self.col))
+
+    def edge_index(self):
+        """The compacted int64 [rows[:E], col[:E]]. SYNCHRONISES the host (it reads the edge count): for
+        inspection, tests and training, not for a rollout loop."""
+        E = int(self.n_edges.item())
+        return [self.rows[:E].to(torch.int64), self.col[:E].to(torch.int64)]
+
+
+def neighbor_args(k, r_cut):
+    """(k, r2_max) of a neighbour graph after the host-side checks: k an integer in [1, 64]; r_cut None
+    (r2_max = +inf) or > 0, squared in float32. ValueError otherwise."""
+    try:
+        k = operator.index(k)
+    except TypeError:
+        k = 0
+    if isinstance(k, bool) or not 1 <= k <= 64:
+        raise ValueError(f"neighbor_graph: k must be an int in [1, 64], got {k!r}")
+    r2 = math.inf
+    if r_cut is not None:
+        if not float(r_cut) > 0:
+            raise ValueError(f"neighbor_graph: r_cut must be > 0 (or None), got {r_cut!r}")
+        with np.errstate(over="ignore"):
+            r2 = float(np.float32(r_cut) * np.float32(r_cut))
+        if not r2 > 0:
+            raise ValueError(f"neighbor_graph: r_cut = {r_cut!r} squares to zero in float32")
+    return k, r2
+
+
+def neighbor_graph(x, batch_size, n_nodes, k, r_cut=None):
+    """The k-nearest-neighbour graph (with r_cut: among the nodes within r_cut) of x [B N, 3], B = batch_size
+    graphs of N = n_nodes consecutive rows, as a NeighborGraph: one nonode_neighbor_graph call, asynchronous,
+    nothing read back. Receiver i keeps the min(k, candidates) nodes j != i of its graph with the smallest
+    (d2, j), d2 = ((dx dx) + (dy dy)) + (dz dz) in individually rounded float32 operations and candidates
+    the j with d2 <= float32(r_cut)^2 (r_cut=None: every j; a NaN distance is never a candidate). The result
+    is a pure function of the positions, bitwise the same from run to run. k in [1, 64]."""
+    from . import _lib
+    B, N = int(batch_size), int(n_nodes)
+    k, r2 = neighbor_args(k, r_cut)
+    if B < 1 or N < 1 or x.dim() != 2 or tuple(x.shape) != (B * N, 3):
+        raise ValueError(f"neighbor_graph: x must be [batch_size * n_nodes, 3] = [{B * N}, 3], got {tuple(x.shape)}")
+    _lib.require_device(x)
+    x = _lib.f32(x)
+    dev = x.device
+    cap = B * N * min(k, N - 1)
+    row_ptr = torch.empty(B * N + 1, dtype=torch.int32, device=dev)
+    col, eid, rows = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
+    L = _lib.lib()
+    ws_bytes = L.nonode_neighbor_graph_workspace_bytes(B, N, k)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+    _lib.check(L.nonode_neighbor_graph(B, N, k, r2, _lib.ptr(x), _lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(eid),
+                                       _lib.ptr(rows), _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
+    return NeighborGraph(rows, col, row_ptr, eid, N)
 
 
 # the second CSR of the reverse pass (EGNO graph="trainable"), cached per edge tensor pair like _csr

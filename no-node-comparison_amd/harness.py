@@ -5,6 +5,11 @@ meaning and return values (EGNO/main_simulation_simple_no.py:311-384, SEGNO/trai
 utils.py:197-219) but run as HIP kernels (csrc/nonode_rollout.hip): the rollouts are ONE C call
 each (segments, re-featurisation and per-frame energies on the device, no host round trip).
 Like the models, these have no CPU path: tensors must be on the ROCm device.
+
+General graphs (models built with graph="any"): prepare_inputs_graph featurises on an explicit edge list,
+and egno_rollout_graph / segno_rollout_graph chain model(...) segments on a k-NN / cut-off graph rebuilt on
+the device from every segment's start (graph.neighbor_graph) or on a fixed list, without a host round trip
+(csrc/nonode_neighbor.hip). The functions above stay full-graph.
 """
 import ctypes
 
@@ -376,3 +381,172 @@ def _segno_rollout_multi(model, h, loc, edge_index, vel, edge_attr, traj_len, nu
         in_steps = torch.tensor(st[1:] + [T], device=loc.device) - T
         edge_attr = torch.cat([prod, loc_dist], 1)
     return preds, (torch.stack(en).unsqueeze(-1) if en else None)
+
+
+# ---- general graphs: featurisation on an explicit list, rollouts on k-NN / cut-off graphs ----
+
+def _graph_source(k, r_cut, edges, who):
+    if (k is None) == (edges is None):
+        raise ValueError(f"{who}: give exactly one of k (a neighbour graph built from the positions, with an "
+                         "optional r_cut) and edges (a fixed list)")
+    if edges is not None and r_cut is not None:
+        raise ValueError(f"{who}: r_cut goes with k (a fixed edge list has no cut-off)")
+    if k is not None:
+        from .graph import neighbor_args
+        neighbor_args(k, r_cut)
+
+
+@torch.no_grad()
+def prepare_inputs_graph(loc, vel, n_nodes, charges=None, t_in=None, *, k=None, r_cut=None, edges=None):
+    """prepare_inputs (main_simulation_simple_no.py:311-339, num_inputs == 1) on an explicit edge list
+    instead of the implicit fully connected one. loc, vel: [B, N, 3] or [F, B, N, 3] with t_in [B] choosing
+    frame t_in - 1 per sample (a python index taken modulo F on the device, as nonode_prepare_inputs takes it:
+    0 is the last frame, and a value past F wraps where python would raise). The graph is either built from the SELECTED positions (k, optional r_cut:
+    graph.neighbor_graph) or given (edges: any [rows, cols] list or a NeighborGraph). Returns
+    (x [BN, 3], v [BN, 3], edge_attr, nodes [BN, 1(+1)], loc_mean [BN, 3], edges) with edge_attr[e] =
+    [q_r q_c, |x_r - x_c|^2] ([|x_r - x_c|^2] without charges), one row per entry of the list; for a
+    NeighborGraph that is [capacity, .] with the rows at or past its device-side edge count zero.
+    Two launches (nonode_prepare_nodes, nonode_edge_features) besides the builder's; memory is
+    O(BN + len(list)) and nothing is read back to the host. Off the autograd tape."""
+    from . import graph as _graph
+    _graph_source(k, r_cut, edges, "prepare_inputs_graph")
+    if loc.dim() not in (3, 4) or loc.shape != vel.shape or loc.shape[-1] != 3:
+        raise ValueError(f"prepare_inputs_graph: loc, vel must be [B, N, 3] or [F, B, N, 3] alike, got "
+                         f"{tuple(loc.shape)}, {tuple(vel.shape)}")
+    if loc.dim() == 3:
+        loc, vel = loc.unsqueeze(0), vel.unsqueeze(0)
+    F, B, N = loc.shape[0], loc.shape[1], loc.shape[2]
+    if N != n_nodes:
+        raise ValueError(f"prepare_inputs_graph: loc has {N} nodes per graph, n_nodes={n_nodes}")
+    BN = B * N
+    if charges is not None and charges.numel() != BN:
+        raise ValueError(f"prepare_inputs_graph: charges must hold {BN} values, got {charges.numel()}")
+    if t_in is not None and t_in.numel() != B:
+        raise ValueError(f"prepare_inputs_graph: t_in must hold one value per sample ({B}), got {t_in.numel()}")
+    if edges is not None:
+        rows, cols = _graph._split(edges)
+        if rows.dim() != 1 or rows.shape != cols.shape or rows.dtype != cols.dtype or \
+                rows.dtype not in (torch.int32, torch.int64):
+            raise ValueError("prepare_inputs_graph: edges must be two 1-D int32 or int64 tensors of one length")
+    _lib.require_device(loc, vel, charges, t_in, *(() if edges is None else (rows, cols)))
+    loc, vel = _f32(loc), _f32(vel)
+    q = _f32(charges).reshape(-1) if charges is not None else None
+    ti = t_in.reshape(-1).to(torch.int32).contiguous() if t_in is not None else None
+    dev = loc.device
+    x = torch.empty(BN, 3, device=dev)
+    v = torch.empty(BN, 3, device=dev)
+    nodes = torch.empty(BN, 2 if q is not None else 1, device=dev)
+    lm = torch.empty(BN, 3, device=dev)
+    L = _lib.lib()
+    s = _lib.stream_of(loc)
+    _lib.check(L.nonode_prepare_nodes(B, N, F, _lib.ptr(loc), _lib.ptr(vel), _lib.ptr(ti), _lib.ptr(q), _lib.ptr(x),
+                                      _lib.ptr(v), _lib.ptr(nodes), _lib.ptr(lm), s))
+    if edges is None:
+        edges = _graph.neighbor_graph(x, B, N, k, r_cut)
+        rows, cols = edges.rows, edges.col
+    n_edges = edges.n_edges if isinstance(edges, _graph.NeighborGraph) else None
+    rows, cols = rows.contiguous(), cols.contiguous()
+    ea = torch.empty(rows.numel(), 2 if q is not None else 1, device=dev)
+    _lib.check(L.nonode_edge_features(rows.numel(), BN, _lib.ptr(rows), _lib.ptr(cols), rows.element_size(),
+                                      _lib.ptr(n_edges), _lib.ptr(x), _lib.ptr(q), _lib.ptr(ea), s))
+    return x, v, ea, nodes, lm, edges
+
+
+def _general_model(model, cls, who):
+    if not isinstance(model, cls):
+        raise TypeError(f"{who} drives no_node_comparison_amd.{cls.__name__} (its packed weights)")
+    if model.graph not in ("any", "trainable"):
+        raise ValueError(f'{who} needs a model built with graph="any" (or "trainable"), got graph={model.graph!r}: '
+                         "the full-graph drivers take the fully connected list")
+
+
+@torch.no_grad()
+def egno_rollout_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, *, k=None, r_cut=None, edges=None,
+                       timesteps_in=None, timesteps_out=None, energy_dataset=None, return_graphs=False):
+    """rollout_fn (main_simulation_simple_no.py:342-384), num_inputs == 1, on a general graph, as a loop of
+    model(...) segments like _egno_rollout_segments. loc, vel [B, N, 3]. Per segment: prepare_inputs_graph
+    on the current frame (k: the neighbour graph is rebuilt from that frame on the device; edges: the
+    topology is fixed and only the features are recomputed), the forward, frame timesteps_in - 1 of each
+    sample (None: the last) as the next input, conserved_energy per frame if asked. Nothing in the loop
+    reads the device. Returns (loc_preds [traj_len*T, BN, 3], energies, energies_allsteps) as egno_rollout
+    does, and with return_graphs=True also the list of the segments' graphs."""
+    from .egno import EGNO
+    _general_model(model, EGNO, "egno_rollout_graph")
+    if model.num_inputs > 1:
+        raise NotImplementedError("egno_rollout_graph rolls the single-input model out (num_inputs == 1)")
+    if model.flat:
+        raise NotImplementedError("egno_rollout_graph does not run with flat=True (general graphs)")
+    _graph_source(k, r_cut, edges, "egno_rollout_graph")
+    T = model.num_timesteps
+    B, N = batch_size, n_nodes
+    BN = B * N
+    if loc.dim() != 3 or tuple(loc.shape) != (B, N, 3) or loc.shape != vel.shape:
+        raise ValueError(f"egno_rollout_graph: loc, vel must be [{B}, {N}, 3], got {tuple(loc.shape)}, "
+                         f"{tuple(vel.shape)}")
+    if timesteps_in is not None and timesteps_in.numel() != B:
+        raise ValueError(f"egno_rollout_graph: timesteps_in must hold one value per sample ({B}), got "
+                         f"{timesteps_in.numel()}")
+    _lib.require_device(loc, vel, charges, model.embedding.weight)
+    dev = loc.device
+    if timesteps_out is None:
+        timesteps_out = torch.arange(T * traj_len, device=dev).unsqueeze(0)
+    if timesteps_out.shape[1] != T * traj_len:
+        raise ValueError(f"timesteps_out must have {T * traj_len} columns")
+    ti = timesteps_in.reshape(-1) if timesteps_in is not None else None   # None: the last frame (t_in = T)
+    preds = torch.empty(traj_len * T, BN, 3, device=dev)
+    en_all, graphs = [], []
+    x, v, edge_attr, nodes, loc_mean, g = prepare_inputs_graph(loc, vel, N, charges, k=k, r_cut=r_cut, edges=edges)
+    for i in range(traj_len):
+        graphs.append(g)
+        t_out = timesteps_out[:, i * T:(i + 1) * T] - i * T
+        x, v, _ = model(x, nodes, g, edge_attr, v=v, loc_mean=loc_mean, timesteps_out=t_out)
+        preds[i * T:(i + 1) * T] = x.reshape(T, BN, 3)
+        if energy_dataset is not None:
+            en_all.append(conserved_energy(energy_dataset, x.reshape(T, BN, 3), v.reshape(T, BN, 3), charges, B))
+        if i + 1 < traj_len:
+            x, v, edge_attr, nodes, loc_mean, g = prepare_inputs_graph(
+                x.reshape(T, B, N, 3), v.reshape(T, B, N, 3), N, charges, ti, k=k, r_cut=r_cut, edges=edges)
+    tail = (graphs,) if return_graphs else ()
+    if energy_dataset is None:
+        return (preds, None, None) + tail
+    en_all = torch.cat(en_all).unsqueeze(-1)
+    return (preds, en_all[T - 1::T], en_all) + tail
+
+
+@torch.no_grad()
+def segno_rollout_graph(model, loc, vel, charges, batch_size, traj_len, num_steps=10, *, k=None, r_cut=None,
+                        edges=None, energy_dataset=None, return_graphs=False):
+    """rollout_fn (train_nbody.py:200-236), num_prev == 1, on a general graph, as a loop of model(...)
+    segments. loc, vel [BN, 3]; his = |v|; num_steps an int or a list of length traj_len. The graph (k:
+    rebuilt on the device; edges: fixed) and the edge attributes [q_r q_c, |x_r - x_c|^2] come from each
+    segment's start and stay frozen over its substeps, as in nonode_segno_forward_step_graph. Nothing in
+    the loop reads the device. Returns (loc_preds [traj_len, BN, 3], energies [traj_len, B, 1] or None), and
+    with return_graphs=True also the list of the segments' graphs."""
+    from .segno import SEGNO
+    _general_model(model, SEGNO, "segno_rollout_graph")
+    if model.bug_compat:
+        raise ValueError("segno_rollout_graph integrates (bug_compat=True would return the inputs every segment)")
+    _graph_source(k, r_cut, edges, "segno_rollout_graph")
+    B = int(batch_size)
+    if loc.dim() != 2 or loc.shape[1] != 3 or loc.shape != vel.shape or B < 1 or loc.shape[0] % B:
+        raise ValueError(f"segno_rollout_graph: loc, vel must be [BN, 3] with BN a multiple of batch_size={B}, got "
+                         f"{tuple(loc.shape)}, {tuple(vel.shape)}")
+    steps = list(num_steps) if isinstance(num_steps, (list, tuple)) else [int(num_steps)] * traj_len
+    if len(steps) != traj_len:
+        raise ValueError("num_steps should be a list of length traj_len")
+    _lib.require_device(loc, vel, charges, model.embedding.weight)
+    BN = loc.shape[0]
+    N = BN // B
+    preds = torch.empty(traj_len, BN, 3, device=loc.device)
+    en, graphs = [], []
+    x, v = loc, vel
+    for i, T in enumerate(steps):
+        x, v, edge_attr, nodes, _, g = prepare_inputs_graph(x.reshape(B, N, 3), v.reshape(B, N, 3), N, charges,
+                                                            k=k, r_cut=r_cut, edges=edges)
+        graphs.append(g)
+        x, _, v = model(nodes[:, :1], x, g, v, edge_attr, T=int(T))
+        preds[i] = x
+        if energy_dataset is not None:
+            en.append(conserved_energy(energy_dataset, x, v, charges, B))
+    tail = (graphs,) if return_graphs else ()
+    return (preds, (torch.stack(en).unsqueeze(-1) if en else None)) + tail

@@ -1,7 +1,7 @@
 """Timings of the general-graph path (EGNO graph="any", csrc/nonode_graph.hip) on the GPU. One JSON
 line per case on stdout (DESIGN.md section 3.7 quotes them; raw lines under profiles/graph/).
 
-python tools/bench_graph.py [--case price|knn|knn_train|all] [--reps 7] [--iters 20] [--arm both|ours]
+python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|all] [--reps 7] [--iters 20] [--arm both|ours]
 
   price  the C2 graph (B = 512, N = 20, T = 10: 5120 fully connected graphs per layer launch) through
          the fused layer entry (nonode_egnn_layer) and, passed as an edge list, through the general one
@@ -17,6 +17,11 @@ python tools/bench_graph.py [--case price|knn|knn_train|all] [--reps 7] [--iters
          parameter's gradient) against fp32 autograd of oracle/torch_ref.egno_forward on the same device,
          alternated likewise. --arm ours runs the HIP arm alone (for a rocprofv3 --kernel-trace --stats run
          of its own: the per-kernel split).
+  knn_rollout  the knn case rolled out: traj_len = 4 segments, the 16-neighbour graph rebuilt from the
+         predicted positions every segment. harness.egno_rollout_graph (device-side builder and featuriser)
+         against the loop a user writes without them: knn_graph below (cdist + topk), torch featurisation
+         on that list, model(graph="any"), alternated likewise. --arm ours runs the first arm alone (for a
+         rocprofv3 --kernel-trace --stats run of its own: the builder's and the featuriser's share).
 Times are device events around `iters` back-to-back calls after a warm-up; each case reports the median
 over the reps and the spread (min, max) beside it.
 """
@@ -31,7 +36,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import no_node_comparison_amd as pkg  # noqa: E402
-from no_node_comparison_amd import _lib, autograd, graph  # noqa: E402
+from no_node_comparison_amd import _lib, autograd, graph, harness  # noqa: E402
 from oracle import torch_ref as tr  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -242,16 +247,81 @@ def case_knn_train(args):
     return res
 
 
+def case_knn_rollout(args):
+    B, N, T, K, SEG, DAMP = 8, 1000, 10, 16, 4, 0.01
+    loc, vel, q = synthetic(B, N, 2)
+    t_out = torch.arange(1, T * SEG + 1, device=DEV).repeat(B, 1)
+    m = model(T, graph="any")
+    # what the undamped model does from these inputs, for the record (one rollout, not timed)
+    up, _, _, ug = harness.egno_rollout_graph(m, loc, vel, q, N, B, SEG, k=K, timesteps_out=t_out, return_graphs=True)
+    undamped = {"segment_absmax": [repr(float(up[i * T:(i + 1) * T].abs().max())) for i in range(SEG)],
+                "segment_n_edges": [int(g.n_edges.item()) for g in ug]}
+    # the untrained model's rollout overflows in the third segment from these inputs (the fourth would then be
+    # timed on an empty graph in one arm and on NaN distances in the other): the last layers of the coordinate
+    # and velocity heads are scaled down so that the positions stay bounded (the line records both rollouts' magnitudes)
+    with torch.no_grad():
+        for layer in m.layers:
+            for head in (layer.coord_net, layer.node_v_net):
+                head.mlp[2].weight.mul_(DAMP)
+                head.mlp[2].bias.mul_(DAMP)
+    qq = q.reshape(-1, 1)
+
+    def ours():
+        return harness.egno_rollout_graph(m, loc, vel, q, N, B, SEG, k=K, timesteps_out=t_out)[0]
+
+    def by_hand():
+        x, v = loc, vel
+        preds = []
+        with torch.no_grad():
+            for i in range(SEG):
+                rows, cols = knn_graph(x, K)
+                x1, v1 = x.reshape(-1, 3), v.reshape(-1, 3)
+                ef = torch.cat([qq[rows] * qq[cols], ((x1[rows] - x1[cols]) ** 2).sum(1, keepdim=True)], 1)
+                h = torch.cat([v1.norm(dim=1, keepdim=True), qq], 1)
+                lm = x.mean(1, keepdim=True).repeat(1, N, 1).reshape(-1, 3)
+                xo, vo, _ = m(x1, h, [rows, cols], ef, v=v1, loc_mean=lm,
+                              timesteps_out=t_out[:, i * T:(i + 1) * T] - i * T)
+                preds.append(xo.reshape(T, B * N, 3))
+                x, v = xo.reshape(T, B, N, 3)[-1], vo.reshape(T, B, N, 3)[-1]
+        return torch.cat(preds)
+
+    arms = {"rollout_graph": ours} if args.arm == "ours" else {"rollout_graph": ours, "by_hand": by_hand}
+    iters = max(args.iters // 4, 3)
+    t = alternate(arms, args.reps, iters)
+    g = stats(t["rollout_graph"])
+    res = {"case": "knn_rollout", "shape": {"graphs": B, "nodes_per_graph": N, "k": K, "T": T, "layers": 4,
+                                            "traj_len": SEG, "capacity": B * N * K},
+           "iters_per_rep": iters,
+           "model": f"untrained, last layers of coord_net and node_v_net scaled by {DAMP} (both arms)",
+           "undamped_rollout": undamped,
+           "rollout_graph": g, "rollout_graph_per_rep_ms": t["rollout_graph"]}
+    last = ours()[-1]
+    res.update({"last_frame_finite": bool(torch.isfinite(last).all()), "last_frame_absmax": float(last.abs().max())})
+    if args.arm != "ours":
+        r = stats(t["by_hand"])
+        a, b = ours(), by_hand()
+        torch.cuda.synchronize()
+        # (the two arms may break a distance tie differently, after which the trajectories part: the first
+        # segment, where both start from the same positions, is the comparable one)
+        res.update({"by_hand_cdist_topk": r, "by_hand_per_rep_ms": t["by_hand"],
+                    "speedup_over_by_hand": r["median_ms"] / g["median_ms"],
+                    "speedup_per_rep": [b_ / a_ for a_, b_ in zip(t["rollout_graph"], t["by_hand"])],
+                    "not_slower_on_any_alternation": all(a_ <= b_ for a_, b_ in zip(t["rollout_graph"], t["by_hand"])),
+                    "first_segment_maxnorm_rel_vs_by_hand": float((a[:T] - b[:T]).abs().max() / b[:T].abs().max())})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", default="all", choices=["price", "knn", "knn_train", "all"])
-    ap.add_argument("--arm", default="both", choices=["both", "ours"], help="knn_train: the HIP arm alone")
+    ap.add_argument("--case", default="all", choices=["price", "knn", "knn_train", "knn_rollout", "all"])
+    ap.add_argument("--arm", default="both", choices=["both", "ours"], help="knn_train, knn_rollout: the HIP arm alone")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_graph.py measures on the GPU: no ROCm device found")
-    for name, fn in (("price", case_price), ("knn", case_knn), ("knn_train", case_knn_train)):
+    for name, fn in (("price", case_price), ("knn", case_knn), ("knn_train", case_knn_train),
+                     ("knn_rollout", case_knn_rollout)):
         if args.case in (name, "all"):
             res = fn(args)
             res["device"] = torch.cuda.get_device_name(0)
