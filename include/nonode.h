@@ -655,7 +655,8 @@ int nonode_segno_forward_step_graph(int n_nodes, long long E, int T, int in_node
  * nonode_neighbor_graph stands in for no reference code: the reference builds only full graphs. It is
  * what a rollout on a k-NN / cut-off graph calls every segment (the drivers harness.egno_rollout_graph /
  * segno_rollout_graph mirror rollout_fn, main_simulation_simple_no.py:342-384 and train_nbody.py:200-236,
- * as loops of model segments over these entries).
+ * as loops of model segments over these entries). Training on such a graph (a taped EGNO forward, the
+ * unrolled harness.egno_rollout_train_graph) also needs its CSR by sender: nonode_neighbor_by_sender below.
  *
  * The batch is B graphs of N consecutive rows of x [B*N][3]. A candidate of receiver i is a node j != i of
  * the same graph with d2 <= r2_max true, where d = x_i - x_j componentwise and
@@ -670,6 +671,29 @@ int nonode_segno_forward_step_graph(int n_nodes, long long E, int T, int in_node
 size_t nonode_neighbor_graph_workspace_bytes(int B, int N, int k);
 int nonode_neighbor_graph(int B, int N, int k, float r2_max, const float* x, int* row_ptr, int* col, int* eid,
                           int* rows, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The same graph as a CSR by sender, which the reverse pass of the graph layer
+ * (nonode_egnn_layer_graph_bwd) walks: what training on a graph rebuilt every step needs, made on the
+ * device from the padded list and its device-side count (nonode_graph_build cannot take a list with a
+ * -1 tail). With E = row_ptr[n_total], read on the device only (held to [0, cap]):
+ *   srow_ptr [n_total + 1]  the exclusive scan of the out-degrees over the entries p < E
+ *   seid [cap]              sender s's positions p < E with col[p] == s, ascending p, at
+ *                           seid[srow_ptr[s] .. srow_ptr[s + 1]): the order (receiver, original index) of
+ *                           nonode_graph_build with rows and cols swapped, as the list is receiver-major
+ *                           and eid the identity; -1 at and past E
+ *   valid [cap]             1 for p < E, 0 for the tail (the backward zeroes the edge_ops rows it marks 0)
+ * No rows / col value at p >= E is used (rows is not read at all); a col[p] outside [0, n_total), which
+ * nonode_neighbor_graph never writes, is skipped. Integer atomics count the out-degrees and claim slots;
+ * a rank sort per sender (one wave per sender, a row of any length: a hub sends to up to N - 1 receivers,
+ * not k) then puts each row in the total order above, so the result is bitwise the same from run to run.
+ * No launch sized from device data. Asynchronous. cap == 0: srow_ptr all zero, nothing else touched.
+ * Workspace: nonode_neighbor_by_sender_workspace_bytes(cap, n_total) (0 for cap < 0 or n_total <= 0).
+ */
+size_t nonode_neighbor_by_sender_workspace_bytes(long long cap, int n_total);
+int nonode_neighbor_by_sender(long long cap, int n_total, const int* rows, const int* col, const int* row_ptr,
+                              int* srow_ptr, int* seid, int* valid, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /*
  * The node side of prepare_inputs (main_simulation_simple_no.py:311-339, num_inputs == 1) without its

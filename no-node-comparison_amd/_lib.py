@@ -43,6 +43,7 @@ SYMBOLS = (
     "nonode_graph_edge_mask", "nonode_egnn_layer_graph_bwd_node_floats", "nonode_egnn_layer_graph_bwd_edge_floats",
     "nonode_egnn_layer_graph_bwd",
     "nonode_neighbor_graph_workspace_bytes", "nonode_neighbor_graph", "nonode_prepare_nodes", "nonode_edge_features",
+    "nonode_neighbor_by_sender_workspace_bytes", "nonode_neighbor_by_sender",
 )
 
 VARIANT_EGNO = 0
@@ -257,6 +258,9 @@ def lib():
     L.nonode_neighbor_graph_workspace_bytes.argtypes = [_i] * 3
     L.nonode_neighbor_graph_workspace_bytes.restype = _sz
     L.nonode_neighbor_graph.argtypes = [_i, _i, _i, _f] + [_vp] * 6 + [_sz, _vp]
+    L.nonode_neighbor_by_sender_workspace_bytes.argtypes = [_ll, _i]
+    L.nonode_neighbor_by_sender_workspace_bytes.restype = _sz
+    L.nonode_neighbor_by_sender.argtypes = [_ll, _i] + [_vp] * 7 + [_sz, _vp]
     L.nonode_prepare_nodes.argtypes = [_i] * 3 + [_vp] * 9
     L.nonode_edge_features.argtypes = [_ll, _i, _vp, _vp, _i] + [_vp] * 5
     L.nonode_profile_begin.argtypes = [_i]

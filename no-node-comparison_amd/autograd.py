@@ -612,7 +612,12 @@ class GraphLayerTrain(torch.autograd.Function):
 
 def egno_graph_train(model, x, h, edge_index, edge_fea, v, loc_mean, t_out):
     """EGNO(graph="trainable").forward on the tape (egno.py:37-111, num_inputs == 1, any edge list): the
-    time embedding and the embedding Linear as torch ops, then one GraphLayerTrain node per layer."""
+    time embedding and the embedding Linear as torch ops, then one GraphLayerTrain node per layer.
+    A graph.NeighborGraph with its CSR by sender runs with E = capacity and edge_fea [capacity, in_edge_nf]:
+    the kernels read only entries the two CSRs name, and the reverse zeroes the edge operand rows of the tail
+    (valid == 0), so nothing here reads the edge count back. No gradient flows through the choice of
+    neighbours (it is discrete) or through edge_fea (detached, as the reference does at
+    main_simulation_simple_no.py:333,338)."""
     from . import graph as _graph
     n = h.shape[0]
     E = _graph._split(edge_index)[0].numel()

@@ -17,7 +17,11 @@
 //   (scan)                  row_ptr = exclusive prefix sum of the degrees (nonode_graph.hip's
 //                           one-workgroup scan)
 //   neighbor_compact_kernel fixed-pitch rows -> CSR (col, rows, eid), and the -1 tail
-//   node_features_kernel    the node side of prepare_inputs (frame choice, |v|, q, per-graph mean)
+//   sender_count / _fill / _sort_kernel  the same graph as a CSR by sender (what the reverse pass of the
+//                           graph layer walks), from the padded list and its device-side count: integer
+//                           atomics count and claim slots, a rank sort per sender then orders each row
+//                           by position, so the result is bitwise reproducible
+//   node_features_kernel   the node side of prepare_inputs (frame choice, |v|, q, per-graph mean)
 //   edge_features_kernel    [q_r q_c, |x_r - x_c|^2] per listed edge below a device-side count
 #include "nonode_common.h"
 
@@ -209,6 +213,54 @@ __global__ __launch_bounds__(256) void edge_features_kernel(long long cap, int n
   }
 }
 
+// ---- the same graph as a CSR by sender (the reverse pass of the graph layer) ----
+// the edge count E = row_ptr[n_total], held to [0, cap]
+__device__ __forceinline__ long long edge_count(const int* __restrict__ row_ptr, int n_total, long long cap) {
+  const long long E = row_ptr[n_total];
+  return E < 0 ? 0 : (E < cap ? E : cap);
+}
+// valid[p] = p < E; every entry below E counts towards its sender's out-degree (a sender outside
+// [0, n_total), which neighbor_graph never writes, is skipped here and in the fill)
+__global__ __launch_bounds__(256) void sender_count_kernel(long long cap, int n_total, const int* __restrict__ col,
+                                                           const int* __restrict__ row_ptr, int* cnt,
+                                                           int* __restrict__ valid) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= cap) return;
+  const bool live = p < edge_count(row_ptr, n_total, cap);
+  valid[p] = live ? 1 : 0;
+  if (!live) return;
+  const int c = col[p];
+  if (c >= 0 && c < n_total) atomicAdd(cnt + c, 1);
+}
+// every entry below E takes the next free slot of its sender's row (any order: sender_sort_kernel
+// orders it); seid starts as -1 everywhere, which is what its tail at and past E keeps
+__global__ __launch_bounds__(256) void sender_fill_kernel(long long cap, int n_total, const int* __restrict__ col,
+                                                          const int* __restrict__ row_ptr, int* cursor,
+                                                          int* __restrict__ tpos, int* __restrict__ seid) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= cap) return;
+  seid[p] = -1;   // (the sort, a later launch, overwrites every position a sender's row covers)
+  if (p >= edge_count(row_ptr, n_total, cap)) return;
+  const int c = col[p];
+  if (c < 0 || c >= n_total) return;
+  tpos[atomicAdd(cursor + c, 1)] = (int)p;
+}
+// one wave per sender: position p goes to its rank among the row's positions (all distinct), so the row
+// is ascending p = (receiver, original index) whatever order the fill claimed its slots in. A row of any
+// length (a hub sends to up to N - 1 receivers): 64 entries per round, each against the whole row.
+__global__ __launch_bounds__(256) void sender_sort_kernel(int n_total, const int* __restrict__ srow_ptr,
+                                                          const int* __restrict__ tpos, int* __restrict__ seid) {
+  const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (s >= n_total) return;
+  const int p0 = srow_ptr[s], d = srow_ptr[s + 1] - p0;
+  for (int i = lane; i < d; i += 64) {
+    const int pi = tpos[p0 + i];
+    int rank = 0;
+    for (int m = 0; m < d; ++m) rank += tpos[p0 + m] < pi ? 1 : 0;
+    seid[p0 + rank] = pi;
+  }
+}
+
 long long neighbor_capacity(int B, int N, int k) { return (long long)B * N * (k < N - 1 ? k : N - 1); }
 
 }  // namespace
@@ -249,6 +301,43 @@ int nonode_neighbor_graph(int B, int N, int k, float r2_max, const float* x, int
   hipLaunchKernelGGL(neighbor_compact_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, cap, n_total, kk,
                      row_ptr, tmp, col, eid, rows);
   return check_launch("neighbor_compact_kernel");
+}
+
+size_t nonode_neighbor_by_sender_workspace_bytes(long long cap, int n_total) {
+  if (cap < 0 || cap >= (1ll << 31) || n_total <= 0) return 0;
+  // the out-degrees / fill cursors, the rows as the fill claimed them
+  return ((size_t)n_total + (size_t)cap) * sizeof(int);
+}
+
+int nonode_neighbor_by_sender(long long cap, int n_total, const int* rows, const int* col, const int* row_ptr,
+                              int* srow_ptr, int* seid, int* valid, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  (void)rows;   // the receiver of an entry is not needed: the list is receiver-major, so ascending p is the order
+  if (cap < 0 || cap >= (1ll << 31) || n_total <= 0 || n_total >= (1 << 30))
+    return fail(NONODE_EINVAL, "neighbor_by_sender: cap=%lld n_total=%d", cap, n_total);
+  if (!srow_ptr) return fail(NONODE_EINVAL, "neighbor_by_sender: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  if (cap == 0) {   // no pair at all
+    if (hipMemsetAsync(srow_ptr, 0, ((size_t)n_total + 1) * sizeof(int), s) != hipSuccess)
+      return fail(NONODE_ELAUNCH, "neighbor_by_sender: memset");
+    return NONODE_OK;
+  }
+  if (!col || !row_ptr || !seid || !valid || !workspace) return fail(NONODE_EINVAL, "neighbor_by_sender: null pointer");
+  if (workspace_bytes < nonode_neighbor_by_sender_workspace_bytes(cap, n_total))
+    return fail(NONODE_EINVAL, "neighbor_by_sender: workspace %zu < %zu", workspace_bytes,
+                nonode_neighbor_by_sender_workspace_bytes(cap, n_total));
+  int* cnt = (int*)workspace;
+  int* tpos = cnt + n_total;
+  if (hipMemsetAsync(cnt, 0, (size_t)n_total * sizeof(int), s) != hipSuccess)
+    return fail(NONODE_ELAUNCH, "neighbor_by_sender: memset");
+  const unsigned blocks = (unsigned)((cap + 255) / 256);
+  hipLaunchKernelGGL(sender_count_kernel, dim3(blocks), dim3(256), 0, s, cap, n_total, col, row_ptr, cnt, valid);
+  if (int rc = check_launch("sender_count_kernel")) return rc;
+  if (int rc = nonode_tu::graph_scan(n_total, cnt, srow_ptr, s)) return rc;
+  hipLaunchKernelGGL(sender_fill_kernel, dim3(blocks), dim3(256), 0, s, cap, n_total, col, row_ptr, cnt, tpos, seid);
+  if (int rc = check_launch("sender_fill_kernel")) return rc;
+  hipLaunchKernelGGL(sender_sort_kernel, dim3((n_total + 3) / 4), dim3(256), 0, s, n_total, srow_ptr, tpos, seid);
+  return check_launch("sender_sort_kernel");
 }
 
 int nonode_prepare_nodes(int B, int N, int F, const float* loc, const float* vel, const int* t_in,

@@ -96,7 +96,11 @@ class EGNO(nn.Module):
     known to be the full one keeps the fused path; "trainable" is "any" whose taped forward (training, or an
     input among x, h, v, loc_mean that requires grad) also runs on every edge list: one autograd node per layer
     (autograd.GraphLayerTrain, csrc/nonode_graph_train.hip), num_inputs=1, not with flat=True. Under "any" and
-    "trainable" `edge_index` may be a graph.NeighborGraph (edge_fea [capacity, in_edge_nf]; off the tape only).
+    "trainable" `edge_index` may be a graph.NeighborGraph (edge_fea [capacity, in_edge_nf], its rows at and
+    past the device-side edge count never read); on the tape ("trainable") it must carry its CSR by sender
+    (graph.neighbor_graph(by_sender=True) / NeighborGraph.with_sender_csr()), and nothing on that path reads
+    the device. No gradient flows through the choice of neighbours (it is discrete), nor through edge_fea
+    (detached, as the reference does at main_simulation_simple_no.py:333,338).
     """
 
     def __init__(self, n_layers, in_node_nf, in_edge_nf, hidden_nf, activation=nn.SiLU(), device='cpu',
@@ -282,11 +286,12 @@ class EGNO(nn.Module):
         if self.graph == "trainable":   # refused before the edge_fea check and before any device work
             if self.flat:
                 raise NotImplementedError('EGNO(graph="trainable") does not run with flat=True')
-            if tapes and isinstance(edge_index, _graph.NeighborGraph):
-                raise NotImplementedError('EGNO(graph="trainable") does not train on a NeighborGraph (the reverse '
-                                          "pass needs the CSR by sender, which is not built from a list with a -1 "
-                                          "tail): train on its compacted list, edges = ng.edge_index(), with "
-                                          "edge_fea[:E]")
+            if tapes and isinstance(edge_index, _graph.NeighborGraph) and not edge_index.has_sender_csr():
+                raise NotImplementedError('EGNO(graph="trainable") does not train on a NeighborGraph without its '
+                                          "CSR by sender, which the reverse pass walks: build the graph with "
+                                          "graph.neighbor_graph(..., by_sender=True) or pass ng.with_sender_csr(); "
+                                          "or train on its compacted list, edges = ng.edge_index() (which "
+                                          "synchronises), with edge_fea[:E]")
             if tapes and self.num_inputs > 1 and _graph.known_full(edge_index, h.shape[-2]) is None:
                 raise NotImplementedError('EGNO(graph="trainable") trains the single-input model (num_inputs=1) '
                                           "on general graphs")

@@ -28,7 +28,10 @@ the mask of the edges the build kept (``csr_by_sender``, cached per edge tensor 
 Neighbour graphs (``neighbor_graph``, csrc/nonode_neighbor.hip): the k-NN / cut-off graph of an equal-size
 batch, built on the device from the positions as a ``NeighborGraph``, which carries its own CSR (valid by
 construction: no check, no cache entry) and goes wherever an edge list goes. A rollout rebuilds it every
-segment (harness.egno_rollout_graph / segno_rollout_graph).
+segment (harness.egno_rollout_graph / segno_rollout_graph). Built with ``by_sender=True`` (or through
+``NeighborGraph.with_sender_csr()``) it also carries the CSR by sender and the tail mask of the reverse pass,
+made on the device from the padded list (``nonode_neighbor_by_sender``), so EGNO(graph="trainable") trains on
+it with nothing read back (harness.egno_rollout_train_graph unrolls a rollout on such graphs).
 """
 import math
 import operator
@@ -328,13 +331,33 @@ class NeighborGraph:
 
     It behaves as the pair [rows, col] (len 2, indexing, iteration), so it goes wherever an edge list goes:
     EGNO / SEGNO built with graph="any" (and EGNO(graph="trainable") off the tape), graph.csr (which
-    returns this object's own CSR without a launch)."""
+    returns this object's own CSR without a launch).
 
-    def __init__(self, rows, col, row_ptr, eid, n_nodes):
+    Built with ``neighbor_graph(..., by_sender=True)``, or through ``with_sender_csr()``, it also carries the
+    CSR by sender of the reverse pass: ``srow_ptr`` [B N + 1], ``seid`` [capacity] (each sender's positions,
+    ascending; -1 at and past the edge count) and ``valid`` [capacity] (1 below the edge count, 0 for the
+    tail), all None otherwise. With them EGNO(graph="trainable") trains on it (graph.csr_by_sender returns
+    them without a launch); no gradient flows through the choice of neighbours, which is discrete."""
+
+    def __init__(self, rows, col, row_ptr, eid, n_nodes, *, srow_ptr=None, seid=None, valid=None):
         self.rows, self.col, self.row_ptr, self.eid = rows, col, row_ptr, eid
         self.capacity = rows.numel()
         self.n_edges = row_ptr[-1:]
         self.n_nodes = n_nodes
+        self.srow_ptr, self.seid, self.valid = srow_ptr, seid, valid
+
+    def has_sender_csr(self):
+        return self.srow_ptr is not None and self.seid is not None and self.valid is not None
+
+    def with_sender_csr(self):
+        """This graph with its CSR by sender: self if it has one, else a NeighborGraph over the same
+        tensors plus srow_ptr, seid, valid (one nonode_neighbor_by_sender call on the current stream,
+        asynchronous, nothing read back). What lets a graph that came out of a rollout be trained on."""
+        if self.has_sender_csr():
+            return self
+        srow_ptr, seid, valid = _sender_csr(self.rows, self.col, self.row_ptr)
+        return NeighborGraph(self.rows, self.col, self.row_ptr, self.eid, self.n_nodes, srow_ptr=srow_ptr,
+                             seid=seid, valid=valid)
 
     def __len__(self):
         return 2
@@ -372,13 +395,34 @@ def neighbor_args(k, r_cut):
     return k, r2
 
 
-def neighbor_graph(x, batch_size, n_nodes, k, r_cut=None):
+def _sender_csr(rows, col, row_ptr):
+    """(srow_ptr, seid, valid) of a device-built graph: nonode_neighbor_by_sender on the padded list and its
+    device-side count, on the stream of `rows`."""
+    from . import _lib
+    _lib.require_device(rows, col, row_ptr)
+    dev = row_ptr.device
+    cap, n_total = rows.numel(), row_ptr.numel() - 1
+    srow_ptr = torch.empty(n_total + 1, dtype=torch.int32, device=dev)
+    seid, valid = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(2))
+    L = _lib.lib()
+    ws_bytes = L.nonode_neighbor_by_sender_workspace_bytes(cap, n_total)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+    _lib.check(L.nonode_neighbor_by_sender(cap, n_total, _lib.ptr(rows), _lib.ptr(col), _lib.ptr(row_ptr),
+                                           _lib.ptr(srow_ptr), _lib.ptr(seid), _lib.ptr(valid), _lib.ptr(ws),
+                                           ws_bytes, _lib.stream_of(row_ptr)))
+    return srow_ptr, seid, valid
+
+
+def neighbor_graph(x, batch_size, n_nodes, k, r_cut=None, *, by_sender=False):
     """The k-nearest-neighbour graph (with r_cut: among the nodes within r_cut) of x [B N, 3], B = batch_size
     graphs of N = n_nodes consecutive rows, as a NeighborGraph: one nonode_neighbor_graph call, asynchronous,
     nothing read back. Receiver i keeps the min(k, candidates) nodes j != i of its graph with the smallest
     (d2, j), d2 = ((dx dx) + (dy dy)) + (dz dz) in individually rounded float32 operations and candidates
     the j with d2 <= float32(r_cut)^2 (r_cut=None: every j; a NaN distance is never a candidate). The result
-    is a pure function of the positions, bitwise the same from run to run. k in [1, 64]."""
+    is a pure function of the positions, bitwise the same from run to run. k in [1, 64].
+    by_sender=True also builds the CSR by sender (NeighborGraph.srow_ptr, seid, valid: one
+    nonode_neighbor_by_sender call on the same stream), which training on the graph needs. The graph is a
+    discrete function of x: nothing here is differentiable, and no gradient flows through it."""
     from . import _lib
     B, N = int(batch_size), int(n_nodes)
     k, r2 = neighbor_args(k, r_cut)
@@ -395,7 +439,10 @@ def neighbor_graph(x, batch_size, n_nodes, k, r_cut=None):
     ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
     _lib.check(L.nonode_neighbor_graph(B, N, k, r2, _lib.ptr(x), _lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(eid),
                                        _lib.ptr(rows), _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
-    return NeighborGraph(rows, col, row_ptr, eid, N)
+    if not by_sender:
+        return NeighborGraph(rows, col, row_ptr, eid, N)
+    srow_ptr, seid, valid = _sender_csr(rows, col, row_ptr)
+    return NeighborGraph(rows, col, row_ptr, eid, N, srow_ptr=srow_ptr, seid=seid, valid=valid)
 
 
 # the second CSR of the reverse pass (EGNO graph="trainable"), cached per edge tensor pair like _csr
@@ -407,7 +454,18 @@ def csr_by_sender(edge_index, n_nodes, device=None):
     the graph layer: the same edge list as a CSR by SENDER (nonode_graph_build with rows and cols swapped;
     each row ordered by (receiver, original index), seid the original edge index), and the mask of the
     edges the build kept (None for a host list, which was range-checked: every edge is kept). Cached per
-    edge tensor pair, as csr is; a device list's bad index goes through csr's flag mechanism."""
+    edge tensor pair, as csr is; a device list's bad index goes through csr's flag mechanism.
+    A NeighborGraph that carries its sender CSR (neighbor_graph(by_sender=True) / with_sender_csr()) gives
+    its own (srow_ptr, seid, valid): no launch, no cache entry. One without it raises ValueError."""
+    if isinstance(edge_index, NeighborGraph):
+        covered = edge_index.row_ptr.numel() - 1
+        if n_nodes != covered:
+            raise ValueError(f"csr_by_sender: the NeighborGraph covers {covered} nodes, n_nodes = {n_nodes}")
+        if not edge_index.has_sender_csr():
+            raise ValueError("csr_by_sender: this NeighborGraph carries no CSR by sender (its list has a -1 tail, "
+                             "which nonode_graph_build does not take): build it with neighbor_graph(by_sender=True) "
+                             "or call with_sender_csr()")
+        return edge_index.srow_ptr, edge_index.seid, edge_index.valid
     rows, cols = _split(edge_index)
     row_ptr, _, eid = csr(edge_index, n_nodes, device)   # checks, polls, and the receiver CSR's cache
     dev = row_ptr.device

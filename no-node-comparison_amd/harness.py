@@ -396,8 +396,7 @@ def _graph_source(k, r_cut, edges, who):
         neighbor_args(k, r_cut)
 
 
-@torch.no_grad()
-def prepare_inputs_graph(loc, vel, n_nodes, charges=None, t_in=None, *, k=None, r_cut=None, edges=None):
+def prepare_inputs_graph(loc, vel, n_nodes, charges=None, t_in=None, *, k=None, r_cut=None, edges=None, tape=False):
     """prepare_inputs (main_simulation_simple_no.py:311-339, num_inputs == 1) on an explicit edge list
     instead of the implicit fully connected one. loc, vel: [B, N, 3] or [F, B, N, 3] with t_in [B] choosing
     frame t_in - 1 per sample (a python index taken modulo F on the device, as nonode_prepare_inputs takes it:
@@ -407,7 +406,44 @@ def prepare_inputs_graph(loc, vel, n_nodes, charges=None, t_in=None, *, k=None, 
     [q_r q_c, |x_r - x_c|^2] ([|x_r - x_c|^2] without charges), one row per entry of the list; for a
     NeighborGraph that is [capacity, .] with the rows at or past its device-side edge count zero.
     Two launches (nonode_prepare_nodes, nonode_edge_features) besides the builder's; memory is
-    O(BN + len(list)) and nothing is read back to the host. Off the autograd tape."""
+    O(BN + len(list)) and nothing is read back to the host. Off the autograd tape by default.
+
+    tape=True (training on the graph): a graph built here (k) carries its CSR by sender
+    (graph.neighbor_graph(by_sender=True)), and with gradients enabled and a loc or vel that requires grad
+    the returned x, v and loc_mean are on the autograd tape (backward: nonode_prepare_inputs_bwd, as
+    prepare_inputs' own: the selected frame gets g_x + the per-graph mean of g_loc_mean, and g_v; every
+    other frame zero). nodes, edge_attr and the graph are not differentiable: the reference detaches the
+    first two (main_simulation_simple_no.py:333,338), and the choice of neighbours is discrete, built from
+    the detached positions, so no gradient flows through it."""
+    if tape and torch.is_grad_enabled() and (loc.requires_grad or vel.requires_grad):
+        box = []
+        x, v, lm, ea, nodes = _PrepareInputsGraph.apply(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, box)
+        return x, v, ea, nodes, lm, box[0]
+    with torch.no_grad():
+        return _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, bool(tape))
+
+
+class _PrepareInputsGraph(torch.autograd.Function):
+    """prepare_inputs_graph on the autograd tape for loc and vel: _PrepareInputs with the featurisation on an
+    explicit list. The graph (not a tensor) leaves through `box`."""
+
+    @staticmethod
+    def forward(ctx, loc, vel, n_nodes, charges, t_in, k, r_cut, edges, box):
+        x, v, ea, nodes, lm, g = _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, True)
+        box.append(g)
+        ctx.shape, ctx.dtypes = tuple(loc.shape), (loc.dtype, vel.dtype)
+        ctx.ti = t_in.reshape(-1).to(torch.int32).contiguous() if t_in is not None else None
+        ctx.mark_non_differentiable(ea, nodes)
+        ctx.set_materialize_grads(False)
+        return x, v, lm, ea, nodes
+
+    @staticmethod
+    def backward(ctx, gx, gv, glm, _gea, _gnodes):
+        return _PrepareInputs.backward(ctx, gx, gv, glm, _gea, _gnodes) + (None, None)
+
+
+def _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, by_sender):
+    """prepare_inputs_graph off the tape (callers hold torch.no_grad())."""
     from . import graph as _graph
     _graph_source(k, r_cut, edges, "prepare_inputs_graph")
     if loc.dim() not in (3, 4) or loc.shape != vel.shape or loc.shape[-1] != 3:
@@ -442,7 +478,7 @@ def prepare_inputs_graph(loc, vel, n_nodes, charges=None, t_in=None, *, k=None, 
     _lib.check(L.nonode_prepare_nodes(B, N, F, _lib.ptr(loc), _lib.ptr(vel), _lib.ptr(ti), _lib.ptr(q), _lib.ptr(x),
                                       _lib.ptr(v), _lib.ptr(nodes), _lib.ptr(lm), s))
     if edges is None:
-        edges = _graph.neighbor_graph(x, B, N, k, r_cut)
+        edges = _graph.neighbor_graph(x, B, N, k, r_cut, by_sender=by_sender)
         rows, cols = edges.rows, edges.col
     n_edges = edges.n_edges if isinstance(edges, _graph.NeighborGraph) else None
     rows, cols = rows.contiguous(), cols.contiguous()
@@ -511,6 +547,58 @@ def egno_rollout_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, 
         return (preds, None, None) + tail
     en_all = torch.cat(en_all).unsqueeze(-1)
     return (preds, en_all[T - 1::T], en_all) + tail
+
+
+def egno_rollout_train_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, *, k=None, r_cut=None,
+                             edges=None, timesteps_in=None, timesteps_out=None, return_graphs=False):
+    """The loop of egno_rollout_graph on the autograd tape (unrolled rollout training on a general graph),
+    num_inputs == 1, for a model built with graph="trainable". loc, vel [B, N, 3]. Per segment:
+    prepare_inputs_graph(tape=True) on the selected frame (k: the neighbour graph, with its CSR by sender, is
+    rebuilt on the device from that frame's detached positions; edges: the list is fixed), then model(...).
+    Returns loc_preds [traj_len*T, BN, 3] with a grad_fn (and with return_graphs=True also the list of the
+    segments' graphs): a loss on it backpropagates through every segment to the parameters and to the
+    initial loc and vel. No gradient flows through the choice of neighbours (it is discrete) or through
+    nodes / edge_attr (detached, as the reference does at main_simulation_simple_no.py:333,338). No
+    energies. Nothing in the loop or in the backward reads the device."""
+    from . import graph as _graph
+    from .egno import EGNO
+    who = "egno_rollout_train_graph"
+    if not isinstance(model, EGNO):
+        raise TypeError(f"{who} drives no_node_comparison_amd.EGNO (its packed weights)")
+    if model.graph != "trainable":
+        raise ValueError(f'{who} needs a model built with graph="trainable", got graph={model.graph!r}')
+    if model.num_inputs > 1:
+        raise NotImplementedError(f"{who} unrolls the single-input model (num_inputs == 1)")
+    if model.flat:
+        raise NotImplementedError(f"{who} does not run with flat=True (general graphs)")
+    _graph_source(k, r_cut, edges, who)
+    T = model.num_timesteps
+    B, N = batch_size, n_nodes
+    BN = B * N
+    if loc.dim() != 3 or tuple(loc.shape) != (B, N, 3) or loc.shape != vel.shape:
+        raise ValueError(f"{who}: loc, vel must be [{B}, {N}, 3], got {tuple(loc.shape)}, {tuple(vel.shape)}")
+    if timesteps_in is not None and timesteps_in.numel() != B:
+        raise ValueError(f"{who}: timesteps_in must hold one value per sample ({B}), got {timesteps_in.numel()}")
+    _lib.require_device(loc, vel, charges, model.embedding.weight)
+    if timesteps_out is None:
+        timesteps_out = torch.arange(T * traj_len, device=loc.device).unsqueeze(0)
+    if timesteps_out.shape[1] != T * traj_len:
+        raise ValueError(f"timesteps_out must have {T * traj_len} columns")
+    ti = timesteps_in.reshape(-1) if timesteps_in is not None else None   # None: the last frame (t_in = T)
+    if isinstance(edges, _graph.NeighborGraph):
+        edges = edges.with_sender_csr()   # (a graph that came out of a rollout)
+    preds, graphs = [], []
+    x, v, t_in = loc, vel, None
+    for i in range(traj_len):
+        x, v, edge_attr, nodes, loc_mean, g = prepare_inputs_graph(x, v, N, charges, t_in, k=k, r_cut=r_cut,
+                                                                   edges=edges, tape=True)
+        graphs.append(g)
+        t_out = timesteps_out[:, i * T:(i + 1) * T] - i * T
+        x, v, _ = model(x, nodes, g, edge_attr, v=v, loc_mean=loc_mean, timesteps_out=t_out)
+        preds.append(x.reshape(T, BN, 3))
+        x, v, t_in = x.reshape(T, B, N, 3), v.reshape(T, B, N, 3), ti
+    preds = torch.cat(preds)
+    return (preds, graphs) if return_graphs else preds
 
 
 @torch.no_grad()

@@ -1,7 +1,7 @@
 """Timings of the general-graph path (EGNO graph="any", csrc/nonode_graph.hip) on the GPU. One JSON
 line per case on stdout (DESIGN.md section 3.7 quotes them; raw lines under profiles/graph/).
 
-python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|all] [--reps 7] [--iters 20] [--arm both|ours]
+python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|knn_rollout_train|all] [--reps 7] [--iters 20] [--arm both|ours]
 
   price  the C2 graph (B = 512, N = 20, T = 10: 5120 fully connected graphs per layer launch) through
          the fused layer entry (nonode_egnn_layer) and, passed as an edge list, through the general one
@@ -22,6 +22,13 @@ python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|all] [--reps
          against the loop a user writes without them: knn_graph below (cdist + topk), torch featurisation
          on that list, model(graph="any"), alternated likewise. --arm ours runs the first arm alone (for a
          rocprofv3 --kernel-trace --stats run of its own: the builder's and the featuriser's share).
+  knn_rollout_train  the knn case trained through an unrolled rollout: traj_len = 2 segments, the graph rebuilt
+         from the predicted positions every segment, forward + backward of a loss on every predicted frame.
+         harness.egno_rollout_train_graph (the padded NeighborGraph with its device-built CSR by sender on the
+         tape, the taped featuriser: nothing read back) against the route without them: per segment
+         ng.edge_index() (one host synchronisation), edge_fea[:E], a taped forward on the compacted list (both
+         CSRs through graph.csr / graph.csr_by_sender's cached-list builds) and the frame choice and loc_mean as
+         torch ops on the tape, alternated likewise. --arm ours runs the first arm alone.
 Times are device events around `iters` back-to-back calls after a warm-up; each case reports the median
 over the reps and the spread (min, max) beside it.
 """
@@ -311,17 +318,82 @@ def case_knn_rollout(args):
     return res
 
 
+def case_knn_rollout_train(args):
+    B, N, T, K, SEG, DAMP = 8, 1000, 10, 16, 2, 0.01
+    loc, vel, q = synthetic(B, N, 2)
+    t_out = torch.arange(1, T * SEG + 1, device=DEV).repeat(B, 1)
+    m = model(T, graph="trainable").train()
+    with torch.no_grad():   # the damped heads of the knn_rollout case: the positions stay bounded over the segments
+        for layer in m.layers:
+            for head in (layer.coord_net, layer.node_v_net):
+                head.mlp[2].weight.mul_(DAMP)
+                head.mlp[2].bias.mul_(DAMP)
+    target = loc.reshape(1, B * N, 3) + 0.1
+
+    def ours():
+        m.zero_grad(set_to_none=True)
+        preds = harness.egno_rollout_train_graph(m, loc, vel, q, N, B, SEG, k=K, timesteps_out=t_out)
+        ((preds - target) ** 2).mean().backward()
+        return preds
+
+    def compacted():
+        m.zero_grad(set_to_none=True)
+        x, v = loc, vel
+        preds = []
+        for i in range(SEG):
+            x1, v1 = x.reshape(-1, 3), v.reshape(-1, 3)
+            _, _, ea, nodes, _, ng = harness.prepare_inputs_graph(x.detach(), v.detach(), N, q, k=K)
+            edges = ng.edge_index()                                   # reads the edge count back
+            lm = x.mean(1, keepdim=True).repeat(1, N, 1).reshape(-1, 3)
+            xo, vo, _ = m(x1, nodes, edges, ea[:edges[0].numel()], v=v1, loc_mean=lm,
+                          timesteps_out=t_out[:, i * T:(i + 1) * T] - i * T)
+            preds.append(xo.reshape(T, B * N, 3))
+            x, v = xo.reshape(T, B, N, 3)[-1], vo.reshape(T, B, N, 3)[-1]
+        preds = torch.cat(preds)
+        ((preds - target) ** 2).mean().backward()
+        return preds
+
+    arms = {"rollout_train_graph": ours} if args.arm == "ours" else {"rollout_train_graph": ours,
+                                                                       "compacted_list": compacted}
+    iters = max(args.iters // 4, 3)
+    t = alternate(arms, args.reps, iters)
+    g = stats(t["rollout_train_graph"])
+    res = {"case": "knn_rollout_train", "shape": {"graphs": B, "nodes_per_graph": N, "k": K, "T": T, "layers": 4,
+                                                  "traj_len": SEG, "capacity": B * N * K},
+           "iters_per_rep": iters,
+           "model": f"untrained, last layers of coord_net and node_v_net scaled by {DAMP} (both arms)",
+           "rollout_train_graph_fwd_bwd": g, "rollout_train_graph_per_rep_ms": t["rollout_train_graph"]}
+    last = ours()[-1].detach()
+    res.update({"last_frame_finite": bool(torch.isfinite(last).all()), "last_frame_absmax": float(last.abs().max())})
+    if args.arm != "ours":
+        r = stats(t["compacted_list"])
+        a = ours().detach()
+        ga = {k_: p.grad.clone() for k_, p in m.named_parameters() if p.grad is not None}
+        b = compacted().detach()
+        torch.cuda.synchronize()
+        gerr = {k_: float((ga[k_] - p.grad).abs().max() / p.grad.abs().max()) for k_, p in m.named_parameters()
+                if p.grad is not None and k_ in ga and float(p.grad.abs().max()) > 0}
+        res.update({"compacted_list_fwd_bwd": r, "compacted_list_per_rep_ms": t["compacted_list"],
+                    "speedup_over_compacted_list": r["median_ms"] / g["median_ms"],
+                    "speedup_per_rep": [b_ / a_ for a_, b_ in zip(t["rollout_train_graph"], t["compacted_list"])],
+                    "faster_on_every_alternation": all(a_ < b_ for a_, b_ in zip(t["rollout_train_graph"],
+                                                                                 t["compacted_list"])),
+                    "preds_maxnorm_rel_vs_compacted_list": float((a - b).abs().max() / b.abs().max()),
+                    "worst_grad_maxnorm_rel_vs_compacted_list": max(gerr.values())})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", default="all", choices=["price", "knn", "knn_train", "knn_rollout", "all"])
-    ap.add_argument("--arm", default="both", choices=["both", "ours"], help="knn_train, knn_rollout: the HIP arm alone")
+    ap.add_argument("--case", default="all", choices=["price", "knn", "knn_train", "knn_rollout", "knn_rollout_train", "all"])
+    ap.add_argument("--arm", default="both", choices=["both", "ours"], help="knn_train, knn_rollout, knn_rollout_train: the HIP arm alone")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_graph.py measures on the GPU: no ROCm device found")
     for name, fn in (("price", case_price), ("knn", case_knn), ("knn_train", case_knn_train),
-                     ("knn_rollout", case_knn_rollout)):
+                     ("knn_rollout", case_knn_rollout), ("knn_rollout_train", case_knn_rollout_train)):
         if args.case in (name, "all"):
             res = fn(args)
             res["device"] = torch.cuda.get_device_name(0)
