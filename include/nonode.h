@@ -650,6 +650,45 @@ int nonode_segno_forward_step_graph(int n_nodes, long long E, int T, int in_node
                                     float* v_out, float* h_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * ---- SEGNO training on an explicit edge list (SEGNO graph="any", trainable=True) ----
+ *
+ * nonode_segno_forward_train_graph: SEGNO.forward_step (SEGNO/models/model.py:95-102) from an embedded h
+ * [n_nodes][64] on the tape, as T calls of the graph layer (SEGNO_GCL.forward, gcl.py:111-119, dt = 1/T,
+ * edge_attr [E][n_edge_feat] frozen). Outputs are bitwise those of nonode_segno_forward_step_graph with
+ * h_in = h. It keeps every substep's inputs and its layer workspace in `state`
+ * (nonode_segno_graph_train_state_bytes(n_nodes, T) = T * n_nodes * 266 floats; n = n_nodes):
+ *   hs [T][n][64] | ws [T][n * 196] | xs [T][n][3] | vs [T][n][3]
+ * hs[t], xs[t], vs[t]: the inputs of substep t (index 0: copies of h, x, v); ws[t]: that substep's
+ * P [n][64] | Q [n][64] | M [n][64] | F [n][4], the state layout of nonode_egnn_layer_graph above. The
+ * caller keeps `state` alive until the backward. T = 0 copies the inputs through (state may be NULL);
+ * E = 0 is legal. Asynchronous; allocates nothing.
+ *
+ * nonode_segno_layer_graph_bwd: the reverse of ONE substep, SEGNO_GCL.forward (gcl.py:111-119: edge_model
+ * gcl.py:74-83, coord_model's per-edge clamp and segment mean gcl.py:97-102 / 16-24, node_model gcl.py:85-95,
+ * v' = v + coords_weight mean dt, x' = x + v' dt) on the CSRs. Arguments as nonode_egnn_layer_graph_bwd
+ * with n_frames = 1 (h, x, v: the substep's inputs hs[t], xs[t], vs[t]; state: ws[t]; bblob from
+ * nonode_pack_layer_bwd, variant SEGNO), plus dt, coords_weight, recurrent. node_ops [n_nodes][520] and
+ * edge_ops [E][400] keep the layout above, so the caller's weight-gradient GEMMs are shared; the gt, t and
+ * gphi slots (256, 320, 515) carry nothing: the first two are not written and gphi is 0. The edge MLP's
+ * first Linear has input order [h_i, h_j, s, e] (gcl.py:78): its gradient's columns are GA^T h | GB^T h |
+ * gz1^T s | gz1^T e. The clamp passes dL/dF per edge and component where -100 <= r_k c <= 100. No float
+ * atomics, sums in CSR order, rows of dropped edges zero when valid is given; NONODE_EUNSUPPORTED /
+ * NONODE_EINVAL before any launch.
+ */
+size_t nonode_segno_graph_train_state_bytes(int n_nodes, int T);
+int nonode_segno_forward_train_graph(int n_nodes, long long E, int T, int n_edge_feat, const float* h, const float* x,
+                                     const float* v, const float* edge_attr, const float* blob, const int* row_ptr,
+                                     const int* col, const int* eid, float coords_weight, int recurrent, float* x_out,
+                                     float* v_out, float* h_out, void* state, size_t state_bytes, void* stream);
+int nonode_segno_layer_graph_bwd(int n_nodes, long long E, int n_edge_feat, const float* h, const float* x,
+                                 const float* v, const float* edge_attr, const float* blob, const float* bblob,
+                                 const float* state, const int* row_ptr, const int* col, const int* eid,
+                                 const int* srow_ptr, const int* seid, const int* valid, const float* g_x,
+                                 const float* g_v, const float* g_h, float dt, float coords_weight, int recurrent,
+                                 float* node_ops, float* edge_ops, float* g_h_in, float* g_x_in, float* g_v_in,
+                                 void* stream);
+
+/*
  * ---- neighbour graphs built on the device, featurisation on an explicit list (csrc/nonode_neighbor.hip) ----
  *
  * nonode_neighbor_graph stands in for no reference code: the reference builds only full graphs. It is

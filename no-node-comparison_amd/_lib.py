@@ -44,6 +44,7 @@ SYMBOLS = (
     "nonode_egnn_layer_graph_bwd",
     "nonode_neighbor_graph_workspace_bytes", "nonode_neighbor_graph", "nonode_prepare_nodes", "nonode_edge_features",
     "nonode_neighbor_by_sender_workspace_bytes", "nonode_neighbor_by_sender",
+    "nonode_segno_graph_train_state_bytes", "nonode_segno_forward_train_graph", "nonode_segno_layer_graph_bwd",
 )
 
 VARIANT_EGNO = 0
@@ -255,6 +256,10 @@ def lib():
     L.nonode_egnn_layer_graph_bwd_edge_floats.argtypes = [_i, _ll]
     L.nonode_egnn_layer_graph_bwd_edge_floats.restype = _sz
     L.nonode_egnn_layer_graph_bwd.argtypes = [_i] * 3 + [_ll] + [_i] * 4 + [_vp] * 22
+    L.nonode_segno_graph_train_state_bytes.argtypes = [_i, _i]
+    L.nonode_segno_graph_train_state_bytes.restype = _sz
+    L.nonode_segno_forward_train_graph.argtypes = [_i, _ll, _i, _i] + [_vp] * 8 + [_f, _i] + [_vp] * 4 + [_sz, _vp]
+    L.nonode_segno_layer_graph_bwd.argtypes = [_i, _ll, _i] + [_vp] * 16 + [_f, _f, _i] + [_vp] * 6
     L.nonode_neighbor_graph_workspace_bytes.argtypes = [_i] * 3
     L.nonode_neighbor_graph_workspace_bytes.restype = _sz
     L.nonode_neighbor_graph.argtypes = [_i, _i, _i, _f] + [_vp] * 6 + [_sz, _vp]

@@ -503,14 +503,65 @@ def graph_frame_groups(n_frames, E, cap_bytes=None):
     return [(f0, min(f0 + per, n_frames)) for f0 in range(0, n_frames, per)]
 
 
+def graph_w1_columns(variant, e1, e1h, ne):
+    """The gradient of the edge MLP's first Linear [64, 129 + ne] from the two products that hold its parts:
+    e1 = [gz1 | gz2]^T [a | 1, s, e] (rows 0..63: column 65 the radial input s, columns 66.. the ne edge
+    features) and e1h = [GA | GB]^T h [128, 64] (rows 0..63 the h_i block, 64..127 the h_j block). EGNO's
+    input order is [s, h_i, h_j, e] (basic.py:152-154), SEGNO's [h_i, h_j, s, e] (gcl.py:78). A pure function
+    of its arguments (any device)."""
+    s_col, e_cols = e1[:64, 65:66], ([e1[:64, 66:66 + ne]] if ne else [])
+    if variant == _lib.VARIANT_EGNO:
+        return torch.cat([s_col, e1h[:64], e1h[64:]] + e_cols, 1)
+    return torch.cat([e1h[:64], e1h[64:], s_col] + e_cols, 1)
+
+
+def _graph_weight_grads(variant, nops, eops, hs, Ms, gho, ne, E):
+    """The 16 parameter gradients (nonode_layer_weights order) of the rows of one operand group: nops [rows, 520],
+    eops [.., 400] as the reverse kernels wrote them, hs / Ms the layer inputs and message sums of those rows
+    (Ms in the state's log2-domain scale), gho the gradient of h_out for them (None = 0). SEGNO has no
+    node_v MLP: its four entries are None (the gt, t and gphi slots of nops are not read)."""
+    dev = nops.device
+    N_, E_ = _GN, _GE
+    nc = lambda k, w=64: nops[:, N_[k]:N_[k] + w]  # noqa: E731
+    hM = torch.cat([hs, Ms * _NEG_LN2], 1)
+    gz, z_ = nc("GZ"), nc("Z")
+    # node level: [GA | GB]^T h, gt^T h, gz^T [h | M], gho^T z, gphi^T t
+    e1h = _tn(nc("GA", 128), hs)
+    if E:
+        # edge level: [gz1 | gz2]^T [a | 1, s, e] and [gz3 | gc]^T [m | 1 | c1]
+        e1 = _tn(eops[:, E_["GZ1"]:E_["GZ1"] + 128], eops[:, E_["A"]:E_["A"] + 72])
+        e2 = _tn(eops[:, E_["GZ3"]:E_["GZ3"] + 65], eops[:, E_["M"]:E_["M"] + 132])
+    else:
+        e1, e2 = torch.zeros(128, 72, device=dev), torch.zeros(65, 132, device=dev)
+    if gho is not None:
+        dn2, dbn2 = _tn(gho, z_), gho.sum(0)
+    else:
+        dn2, dbn2 = torch.zeros(64, 64, device=dev), torch.zeros(64, device=dev)
+    if variant == _lib.VARIANT_EGNO:
+        gt = nc("GT")
+        gphi = nops[:, N_["GF"] + 3:N_["GF"] + 4]
+        node_v = [_tn(gt, hs), gt.sum(0), _tn(gphi, nc("T")), gphi.sum(0)]
+    else:
+        node_v = [None] * 4
+    return [graph_w1_columns(variant, e1, e1h, ne), e1[:64, 64], e1[64:, :64], e1[64:, 64],   # edge MLP
+            e2[:64, :64], e2[:64, 64], e2[64:, 68:132], e2[64, 64:65],                         # coord MLP
+            *node_v,                                                                           # node_v MLP
+            _tn(gz, hM), gz.sum(0), dn2, dbn2]                                                 # node MLP
+
+
 def graph_layer_reverse(n_frames, n, E, ne, ef_frames, h, x, v, ef, blob, bblob, state, csr, scsr, gx, gv, gh,
-                        cap_bytes=None, want_w=True):
-    """nonode_egnn_layer_graph_bwd over the frame groups plus the weight-gradient GEMMs. h [n_frames*n, 64],
+                        cap_bytes=None, want_w=True, variant=_lib.VARIANT_EGNO, segno=None):
+    """The reverse of the graph layer plus the weight-gradient GEMMs. h [n_frames*n, 64],
     x, v [.., 3], ef [ef_frames * E, ne] (f32, contiguous), state: the workspace nonode_egnn_layer_graph
     filled, csr = (row_ptr, col, eid), scsr = (srow_ptr, seid, valid) of graph.csr / graph.csr_by_sender,
     gx, gv, gh: gradients of the layer's outputs (None = 0). Returns (g_h_in, g_x_in, g_v_in, grads) with
-    grads the 16 parameter gradients in nonode_layer_weights order (edge, coord, node_v, node MLP; the first
-    Linear's columns [s, h_i, h_j, e]; None with want_w=False, a frozen model's input gradients)."""
+    grads the 16 parameter gradients in nonode_layer_weights order (edge, coord, node_v, node MLP; None with
+    want_w=False, a frozen model's input gradients).
+    variant EGNO (the default): nonode_egnn_layer_graph_bwd over the frame groups; the first Linear's columns
+    [s, h_i, h_j, e]. variant SEGNO with segno = (dt, coords_weight, recurrent): ONE substep (n_frames =
+    ef_frames = 1) through nonode_segno_layer_graph_bwd; the first Linear's columns [h_i, h_j, s, e]
+    (gcl.py:78) and the four node_v gradients None (autograd.segno_graph_reverse walks the substeps and
+    groups their operands itself)."""
     L = _lib.lib()
     dev = h.device
     nt = n_frames * n
@@ -518,9 +569,17 @@ def graph_layer_reverse(n_frames, n, E, ne, ef_frames, h, x, v, ef, blob, bblob,
     srow_ptr, seid, valid = scsr
     g_h, g_x, g_v = torch.empty(nt, 64, device=dev), torch.empty(nt, 3, device=dev), torch.empty(nt, 3, device=dev)
     M = state[2 * nt * 64:3 * nt * 64].view(nt, 64)
-    ef3 = ef.reshape(ef_frames, E, ne) if ne else None
     s = _lib.stream_of(h)
     N_, E_ = _GN, _GE
+    if variant != _lib.VARIANT_EGNO:
+        if n_frames != 1 or ef_frames != 1 or segno is None:
+            raise ValueError("graph_layer_reverse: SEGNO reverses one substep (n_frames = ef_frames = 1) with "
+                             "segno=(dt, coords_weight, recurrent)")
+        nops = torch.empty(n, N_["STRIDE"], device=dev)
+        eops = torch.empty(E, E_["STRIDE"], device=dev)
+        _segno_substep_bwd(L, n, E, ne, h, x, v, ef, blob, bblob, state, csr, scsr, gx, gv, gh, segno, nops, eops,
+                           g_h, g_x, g_v, s)
+        return g_h, g_x, g_v, (_graph_weight_grads(variant, nops, eops, h, M, gh, ne, E) if want_w else None)
     total = None
     for f0, f1 in graph_frame_groups(n_frames, E, cap_bytes):
         nf = f1 - f0
@@ -533,31 +592,23 @@ def graph_layer_reverse(n_frames, n, E, ne, ef_frames, h, x, v, ef, blob, bblob,
             _lib.ptr(gh), _lib.ptr(nops), _lib.ptr(eops) if E else None, _lib.ptr(g_h), _lib.ptr(g_x), _lib.ptr(g_v), s))
         if not want_w:
             continue
-        nc = lambda k, w=64: nops[:, N_[k]:N_[k] + w]  # noqa: E731
-        hs = h[f0 * n:f1 * n]
-        hM = torch.cat([hs, M[f0 * n:f1 * n] * _NEG_LN2], 1)
-        gz, z_, gt = nc("GZ"), nc("Z"), nc("GT")
-        gphi = nops[:, N_["GF"] + 3:N_["GF"] + 4]
-        # node level: [GA | GB]^T h, gt^T h, gz^T [h | M], gho^T z, gphi^T t
-        e1h = _tn(nc("GA", 128), hs)
-        if E:
-            # edge level: [gz1 | gz2]^T [a | 1, s, e] and [gz3 | gc]^T [m | 1 | c1]
-            e1 = _tn(eops[:, E_["GZ1"]:E_["GZ1"] + 128], eops[:, E_["A"]:E_["A"] + 72])
-            e2 = _tn(eops[:, E_["GZ3"]:E_["GZ3"] + 65], eops[:, E_["M"]:E_["M"] + 132])
-        else:
-            e1, e2 = torch.zeros(128, 72, device=dev), torch.zeros(65, 132, device=dev)
-        w1 = [e1[:64, 65:66], e1h[:64], e1h[64:]] + ([e1[:64, 66:66 + ne]] if ne else [])
-        if gh is not None:
-            gho = gh[f0 * n:f1 * n]
-            dn2, dbn2 = _tn(gho, z_), gho.sum(0)
-        else:
-            dn2, dbn2 = torch.zeros(64, 64, device=dev), torch.zeros(64, device=dev)
-        grads = [torch.cat(w1, 1), e1[:64, 64], e1[64:, :64], e1[64:, 64],            # edge MLP
-                 e2[:64, :64], e2[:64, 64], e2[64:, 68:132], e2[64, 64:65],            # coord MLP
-                 _tn(gt, hs), gt.sum(0), _tn(gphi, nc("T")), gphi.sum(0),              # node_v MLP
-                 _tn(gz, hM), gz.sum(0), dn2, dbn2]                                    # node MLP
+        grads = _graph_weight_grads(variant, nops, eops, h[f0 * n:f1 * n], M[f0 * n:f1 * n],
+                                    gh[f0 * n:f1 * n] if gh is not None else None, ne, E)
         total = grads if total is None else [a + b for a, b in zip(total, grads)]
     return g_h, g_x, g_v, total
+
+
+def _segno_substep_bwd(L, n, E, ne, h, x, v, ef, blob, bblob, ws, csr, scsr, gx, gv, gh, segno, nops, eops, g_h, g_x,
+                       g_v, s):
+    """nonode_segno_layer_graph_bwd of one substep (h, x, v: its inputs; ws: its layer workspace)."""
+    row_ptr, col, eid = csr
+    srow_ptr, seid, valid = scsr
+    dt, cw, recurrent = segno
+    _lib.check(L.nonode_segno_layer_graph_bwd(
+        n, E, ne, _lib.ptr(h), _lib.ptr(x), _lib.ptr(v), _lib.ptr(ef) if ne else None, _lib.ptr(blob), _lib.ptr(bblob),
+        _lib.ptr(ws), _lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(eid), _lib.ptr(srow_ptr), _lib.ptr(seid),
+        _lib.ptr(valid), _lib.ptr(gx), _lib.ptr(gv), _lib.ptr(gh), float(dt), float(cw), int(bool(recurrent)),
+        _lib.ptr(nops), _lib.ptr(eops) if E else None, _lib.ptr(g_h), _lib.ptr(g_x), _lib.ptr(g_v), s))
 
 
 class GraphLayerTrain(torch.autograd.Function):
@@ -625,3 +676,176 @@ def egno_graph_train(model, x, h, edge_index, edge_fea, v, loc_mean, t_out):
     scsr = _graph.csr_by_sender(edge_index, n, device=x.device)
     hh, xx, vv, lm = _embed_frames(model, x, h, v, loc_mean, t_out, n)
     return _layer_tape(model, GraphLayerTrain, (n, E, (csr, scsr)), hh, xx, vv, lm, edge_fea)
+
+
+# ---- SEGNO(graph="any", trainable=True) training on any edge list ------------------------------------------
+# forward_step's T substeps (model.py:95-102) as ONE autograd node: nonode_segno_forward_train_graph saves
+# every substep's inputs and its layer workspace (T n 266 floats; 1.4 GB at n = 25,600 and 50 substeps), the
+# backward walks the substeps T-1 .. 0 through nonode_segno_layer_graph_bwd. The operand rows of several
+# substeps go into one buffer (the frame-group mechanism with substeps in place of frames, bounded by
+# GRAPH_OPS_CAP_BYTES / model.graph_ops_cap_bytes) and each group gets one set of weight-gradient GEMMs,
+# added in the order of the walk.
+
+def _segno_graph_state(state, T, n):
+    """(hs [T, n, 64], ws [T, n * 196], xs [T, n, 3], vs [T, n, 3]) views of the training forward's state
+    (include/nonode.h: nonode_segno_forward_train_graph)."""
+    o1, o2, o3 = T * n * 64, T * n * 260, T * n * 263
+    return (state[:o1].view(T, n, 64), state[o1:o2].view(T, n * 196), state[o2:o3].view(T, n, 3),
+            state[o3:T * n * 266].view(T, n, 3))
+
+
+def _segno_graph_forward(ctx, model, h, x, v, edge_attr, T, graph):
+    """nonode_segno_forward_train_graph from an embedded h (f32, contiguous): (x, h, v) after T substeps; ctx
+    keeps the saved state for segno_graph_reverse. graph = (n, E, csr, scsr)."""
+    L = _lib.lib()
+    n, E, csr, _ = graph
+    dev = x.device
+    x, v, ea = _f32(x), _f32(v), _f32(edge_attr)
+    blob = model._packed()
+    x_out, v_out, h_out = (torch.empty(n, k, device=dev) for k in (3, 3, model.hidden_nf))
+    st_bytes = L.nonode_segno_graph_train_state_bytes(n, T)
+    state = torch.empty(st_bytes // 4, dtype=torch.float32, device=dev)
+    _lib.check(L.nonode_segno_forward_train_graph(
+        n, E, T, model.in_edge_nf, _lib.ptr(h), _lib.ptr(x), _lib.ptr(v), _lib.ptr(ea) if model.in_edge_nf else None,
+        _lib.ptr(blob), _lib.ptr(csr[0]), _lib.ptr(csr[1]), _lib.ptr(csr[2]), float(model.coords_weight),
+        int(bool(model.recurrent)), _lib.ptr(x_out), _lib.ptr(v_out), _lib.ptr(h_out), _lib.ptr(state), st_bytes,
+        _lib.stream_of(x)))
+    ctx.model, ctx.T, ctx.graph, ctx.state = model, T, graph, state
+    ctx.set_materialize_grads(False)   # unused outputs: None, taken as zero by the reverse kernels
+    sink = getattr(model, "_train_ops_sink", None)
+    ctx.ops_sink = sink   # tests: the operand buffers of the backward's groups
+    return (x_out, h_out, v_out), (x, v, ea)
+
+
+def segno_graph_reverse(model, T, graph, state, ea, gx, gh, gv, want_w=True, cap_bytes=None, ops_sink=None):
+    """The reverse of the T substeps: ({GCL parameter name: gradient} or {} with want_w=False, g_h, g_x, g_v)
+    of the inputs. gx, gh, gv: gradients of the outputs (None = 0)."""
+    L = _lib.lib()
+    n, E, csr, scsr = graph
+    ne = model.in_edge_nf
+    dev = state.device
+    if T == 0:   # the inputs passed through
+        return {}, gh, gx, gv
+    gx, gh, gv = _f32(gx), _f32(gh), _f32(gv)
+    blob, bblob = model._packed(), model._packed_bwd()
+    hs, ws, xs, vs = _segno_graph_state(state, T, n)
+    segno = (1.0 / T, model.coords_weight, model.recurrent)
+    s = _lib.stream_of(state)
+    N_, E_ = _GN, _GE
+    total = None
+    for t0, t1 in reversed(graph_frame_groups(T, E, cap_bytes)):
+        g = t1 - t0
+        nops = torch.empty(g * n, N_["STRIDE"], device=dev)
+        eops = torch.empty(g * E, E_["STRIDE"], device=dev)
+        ghos = [None] * g
+        for t in range(t1 - 1, t0 - 1, -1):
+            k = t - t0
+            ghos[k] = gh
+            g_h, g_x, g_v = torch.empty(n, 64, device=dev), torch.empty(n, 3, device=dev), torch.empty(n, 3, device=dev)
+            _segno_substep_bwd(L, n, E, ne, hs[t], xs[t], vs[t], ea, blob, bblob, ws[t], csr, scsr, gx, gv, gh, segno,
+                               nops[k * n:(k + 1) * n], eops[k * E:(k + 1) * E], g_h, g_x, g_v, s)
+            gh, gx, gv = g_h, g_x, g_v
+        if ops_sink is not None:
+            ops_sink.append((t0, t1, nops, eops))
+        if not want_w:
+            continue
+        Ms = torch.cat([ws[t][2 * n * 64:3 * n * 64].view(n, 64) for t in range(t0, t1)])
+        if all(q is None for q in ghos):
+            gho = None
+        else:
+            gho = torch.cat([q if q is not None else torch.zeros(n, 64, device=dev) for q in ghos])
+        grads = _graph_weight_grads(_lib.VARIANT_SEGNO, nops, eops, hs[t0:t1].reshape(g * n, 64), Ms, gho, ne, E)
+        total = grads if total is None else [a + b if a is not None else None for a, b in zip(total, grads)]
+    named = dict(model.named_parameters())
+    out = {}
+    if total is not None:
+        for nm, gr in zip(model.gcl_param_names(), total):
+            if nm is not None:
+                out[nm] = gr.reshape(named[nm].shape).to(named[nm].dtype)
+    return out, gh, gx, gv
+
+
+def _segno_graph_backward(ctx, gx, gh, gv, want_w):
+    model = ctx.model
+    out = segno_graph_reverse(model, ctx.T, ctx.graph, ctx.state, ctx.ea, gx, gh, gv, want_w,
+                              getattr(model, "graph_ops_cap_bytes", None), ctx.ops_sink)
+    ctx.state = None
+    return out
+
+
+class SEGNOGraphStepTrain(torch.autograd.Function):
+    """SEGNO.forward_step (SEGNO/models/model.py:95-102) on any edge list, on the autograd tape: T substeps of
+    SEGNO_GCL (gcl.py:111-119) from an embedded h. It serves forward_step, his wider than 40 features and the
+    multi-input forward (SEGNO._step)."""
+
+    @staticmethod
+    def forward(ctx, model, h, x, v, edge_attr, T, graph, *params):
+        h = _f32(h)
+        outs, (x, v, ea) = _segno_graph_forward(ctx, model, h, x, v, edge_attr, T, graph)
+        ctx.ea = ea
+        # the parameters (the backward repacks their current values) and the inputs through
+        # save_for_backward: an in-place edit of any of them after the forward raises in the backward
+        ctx.save_for_backward(h, x, v, ea, *params)
+        return outs
+
+    @staticmethod
+    def backward(ctx, gx, gh, gv):
+        model = ctx.model
+        _ = ctx.saved_tensors   # the version check
+        grads, g_h, g_x, g_v = _segno_graph_backward(ctx, gx, gh, gv, any(ctx.needs_input_grad[7:]))
+        out = [grads.get(nm) for nm, _ in model.module.named_parameters(prefix="module")]
+        return (None, g_h, g_x, g_v, None, None, None) + tuple(out)
+
+
+def segno_graph_step_train(model, h, x, v, edge_attr, T, graph):
+    """forward_step on any edge list that records the kernels' backward on the autograd tape."""
+    params = [p for _, p in model.module.named_parameters()]
+    return SEGNOGraphStepTrain.apply(model, h, x, v, edge_attr, T, graph, *params)
+
+
+class SEGNOGraphTrain(torch.autograd.Function):
+    """SEGNO.forward in training with one input (SEGNO/models/model.py:53-102) on any edge list: the embedding
+    Linear (model.py:73; nonode_embedding_forward / _backward) and forward_step's T substeps as ONE node of
+    the tape, like SEGNOTrain."""
+
+    @staticmethod
+    def forward(ctx, model, his, x, v, edge_attr, T, graph, *params):
+        L = _lib.lib()
+        ctx.his_dtype = his.dtype
+        his = _f32(his)
+        n = graph[0]
+        h = torch.empty(n, model.hidden_nf, device=x.device)
+        ew, eb = _f32(model.embedding.weight), _f32(model.embedding.bias)
+        _lib.check(L.nonode_embedding_forward(n, his.shape[1], _lib.ptr(his), _lib.ptr(ew), _lib.ptr(eb),
+                                              _lib.ptr(h), _lib.stream_of(his)))
+        outs, (x, v, ea) = _segno_graph_forward(ctx, model, h, x, v, edge_attr, T, graph)
+        ctx.ea = ea
+        ctx.save_for_backward(his, x, v, ea, *params)   # version checks, as SEGNOGraphStepTrain
+        return outs
+
+    @staticmethod
+    def backward(ctx, gx, gh, gv):
+        model = ctx.model
+        his = ctx.saved_tensors[0]
+        want_w = any(ctx.needs_input_grad[7:])
+        grads, g_h, g_x, g_v = _segno_graph_backward(ctx, gx, gh, gv, want_w)
+        gw = gb = g_his = None
+        if g_h is not None and want_w:
+            L = _lib.lib()
+            n, din = his.shape
+            gw = torch.empty_like(model.embedding.weight)
+            gb = torch.empty_like(model.embedding.bias)
+            ws_bytes = L.nonode_embedding_backward_workspace_bytes(n, din)
+            ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=g_h.device)
+            _lib.check(L.nonode_embedding_backward(n, din, _lib.ptr(his), _lib.ptr(g_h), _lib.ptr(gw), _lib.ptr(gb),
+                                                   _lib.ptr(ws), ws_bytes, _lib.stream_of(g_h)))
+        if g_h is not None and ctx.needs_input_grad[1]:   # dL/dhis of the embedding Linear (model.py:73)
+            g_his = (g_h @ _f32(model.embedding.weight)).to(ctx.his_dtype)
+        out = [grads.get(nm) for nm, _ in model.module.named_parameters(prefix="module")]
+        return (None, g_his, g_x, g_v, None, None, None, gw, gb) + tuple(out)
+
+
+def segno_graph_train(model, his, x, v, edge_attr, T, graph):
+    """SEGNO.forward (one input) on any edge list: embedding + T substeps on the autograd tape."""
+    params = [model.embedding.weight, model.embedding.bias] + [p for _, p in model.module.named_parameters()]
+    return SEGNOGraphTrain.apply(model, his, x, v, edge_attr, T, graph, *params)

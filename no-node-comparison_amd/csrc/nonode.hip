@@ -2498,6 +2498,52 @@ int nonode_segno_forward_step_graph(int n_nodes, long long E, int T, int in_node
   return NONODE_OK;
 }
 
+// state of the SEGNO training forward on an edge list (floats, n = n_nodes; layout in nonode.h)
+static size_t segno_graph_state_floats(int n_nodes, int T) { return (size_t)T * (size_t)n_nodes * 266; }
+
+size_t nonode_segno_graph_train_state_bytes(int n_nodes, int T) {
+  if (n_nodes <= 0 || T <= 0) return 0;
+  return segno_graph_state_floats(n_nodes, T) * sizeof(float);
+}
+
+int nonode_segno_forward_train_graph(int n_nodes, long long E, int T, int n_edge_feat, const float* h, const float* x,
+                                     const float* v, const float* edge_attr, const float* blob, const int* row_ptr,
+                                     const int* col, const int* eid, float coords_weight, int recurrent, float* x_out,
+                                     float* v_out, float* h_out, void* state, size_t state_bytes, void* stream) {
+  if (n_nodes <= 0 || E < 0 || T < 0 || n_edge_feat < 0 || n_edge_feat > 4 || (long long)n_nodes * (T > 0 ? T : 1) > (1ll << 30))
+    return fail(NONODE_EUNSUPPORTED, "segno_forward_train_graph: n_nodes=%d E=%lld T=%d ne=%d", n_nodes, E, T, n_edge_feat);
+  if (!h || !x || !v || !blob || !row_ptr || (E > 0 && (!col || !eid || (n_edge_feat > 0 && !edge_attr))) || !x_out ||
+      !v_out || !h_out || (T > 0 && !state))
+    return fail(NONODE_EINVAL, "segno_forward_train_graph: null pointer");
+  if (h_out == h || x_out == x || v_out == v)
+    return fail(NONODE_EINVAL, "segno_forward_train_graph: outputs may not alias inputs");
+  if (state_bytes < nonode_segno_graph_train_state_bytes(n_nodes, T))
+    return fail(NONODE_EINVAL, "segno_forward_train_graph: state too small");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)n_nodes;
+  float* hs = (float*)state;                 // [T][n][64]
+  float* ws = hs + (size_t)T * n * 64;       // [T][n * 196]: P | Q | M | F of each substep
+  float* xs = ws + (size_t)T * n * 196;      // [T][n][3]
+  float* vs = xs + (size_t)T * n * 3;        // [T][n][3]
+  float* h0 = T ? hs : h_out; float* x0 = T ? xs : x_out; float* v0 = T ? vs : v_out;   // T = 0: the inputs pass through
+  if (hipMemcpyAsync(h0, h, n * 64 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(x0, x, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(v0, v, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return fail(NONODE_ELAUNCH, "segno_forward_train_graph: copy");
+  // substep t reads its saved inputs and writes substep t + 1's (the last one: the outputs); its layer
+  // workspace is the state the reverse reads (model.py:95-102, dt = 1/T)
+  for (int t = 0; t < T; ++t) {
+    const bool last = t == T - 1;
+    if (int rc = nonode_tu::graph_layer(NONODE_VARIANT_SEGNO, 1, n_nodes, E, n_edge_feat, 1, hs + t * n * 64,
+                                        xs + t * n * 3, vs + t * n * 3, edge_attr, blob, row_ptr, col, eid,
+                                        1.0f / (float)T, coords_weight, recurrent, last ? h_out : hs + (t + 1) * n * 64,
+                                        last ? x_out : xs + (t + 1) * n * 3, last ? v_out : vs + (t + 1) * n * 3,
+                                        ws + t * n * 196, s))
+      return rc;
+  }
+  return NONODE_OK;
+}
+
 int nonode_profile_begin(int max_records) {
   std::lock_guard<std::mutex> lk(g_prof.mu);
   if (max_records <= 0 || max_records > (1 << 20)) return fail(NONODE_EINVAL, "profile_begin: %d", max_records);

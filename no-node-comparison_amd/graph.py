@@ -22,16 +22,18 @@ by receiver (``csr``, one ``nonode_graph_build`` per edge tensor pair, cached th
 graph kernels of csrc/nonode_graph.hip walk. An index outside [0, n_nodes) raises ValueError at once for a
 host list; for a device list it goes through the same flag / ``finish()`` / deferred ValueError mechanism,
 with ``nonode_graph_build`` as the flag's writer (it drops the bad edge, so no kernel reads out of range).
-Training on such a list (``EGNO(graph="trainable")``) also needs the CSR by sender and, for a device list,
-the mask of the edges the build kept (``csr_by_sender``, cached per edge tensor pair as well).
+Training on such a list (``EGNO(graph="trainable")``, ``SEGNO(graph="any", trainable=True)``) also needs the CSR by
+sender and, for a device list, the mask of the edges the build kept (``csr_by_sender``, cached per edge tensor pair
+as well).
 
 Neighbour graphs (``neighbor_graph``, csrc/nonode_neighbor.hip): the k-NN / cut-off graph of an equal-size
 batch, built on the device from the positions as a ``NeighborGraph``, which carries its own CSR (valid by
 construction: no check, no cache entry) and goes wherever an edge list goes. A rollout rebuilds it every
 segment (harness.egno_rollout_graph / segno_rollout_graph). Built with ``by_sender=True`` (or through
 ``NeighborGraph.with_sender_csr()``) it also carries the CSR by sender and the tail mask of the reverse pass,
-made on the device from the padded list (``nonode_neighbor_by_sender``), so EGNO(graph="trainable") trains on
-it with nothing read back (harness.egno_rollout_train_graph unrolls a rollout on such graphs).
+made on the device from the padded list (``nonode_neighbor_by_sender``), so EGNO(graph="trainable") and
+SEGNO(graph="any", trainable=True) train on it with nothing read back (harness.egno_rollout_train_graph /
+segno_rollout_train_graph unroll a rollout on such graphs).
 """
 import math
 import operator
@@ -336,8 +338,8 @@ class NeighborGraph:
     Built with ``neighbor_graph(..., by_sender=True)``, or through ``with_sender_csr()``, it also carries the
     CSR by sender of the reverse pass: ``srow_ptr`` [B N + 1], ``seid`` [capacity] (each sender's positions,
     ascending; -1 at and past the edge count) and ``valid`` [capacity] (1 below the edge count, 0 for the
-    tail), all None otherwise. With them EGNO(graph="trainable") trains on it (graph.csr_by_sender returns
-    them without a launch); no gradient flows through the choice of neighbours, which is discrete."""
+    tail), all None otherwise. With them EGNO(graph="trainable") and SEGNO(graph="any", trainable=True) train on it
+    (graph.csr_by_sender returns them without a launch); no gradient flows through the choice of neighbours, which is discrete."""
 
     def __init__(self, rows, col, row_ptr, eid, n_nodes, *, srow_ptr=None, seid=None, valid=None):
         self.rows, self.col, self.row_ptr, self.eid = rows, col, row_ptr, eid

@@ -638,3 +638,49 @@ def segno_rollout_graph(model, loc, vel, charges, batch_size, traj_len, num_step
             en.append(conserved_energy(energy_dataset, x, v, charges, B))
     tail = (graphs,) if return_graphs else ()
     return (preds, (torch.stack(en).unsqueeze(-1) if en else None)) + tail
+
+
+def segno_rollout_train_graph(model, loc, vel, charges, batch_size, traj_len, num_steps=10, *, k=None, r_cut=None,
+                              edges=None, return_graphs=False):
+    """The loop of segno_rollout_graph on the autograd tape (unrolled rollout training on a general graph),
+    num_prev == 1, for a model built with graph="any", trainable=True. loc, vel [BN, 3]; num_steps an int or a
+    list of length traj_len. Per segment: prepare_inputs_graph(tape=True) on the previous segment's predicted
+    x, v (k: the neighbour graph, with its CSR by sender, is rebuilt on the device from the detached positions;
+    edges: the list is fixed), then model(...). Returns loc_preds [traj_len, BN, 3] with a grad_fn (and with
+    return_graphs=True also the list of the segments' graphs): a loss on it backpropagates through every segment
+    to the parameters and to the initial loc and vel. No gradient flows through the choice of neighbours (it is
+    discrete) or through his = |v| and edge_attr (detached: the reference builds them from data,
+    train_nbody.py:121-123,230-233, as egno_rollout_train_graph does). No energies. Nothing in the loop or in
+    the backward reads the device."""
+    from . import graph as _graph
+    from .segno import SEGNO
+    who = "segno_rollout_train_graph"
+    if not isinstance(model, SEGNO):
+        raise TypeError(f"{who} drives no_node_comparison_amd.SEGNO (its packed weights)")
+    if model.graph != "any" or not model.trainable:
+        raise ValueError(f'{who} needs a model built with graph="any", trainable=True, got graph={model.graph!r}, '
+                         f"trainable={model.trainable!r}")
+    if model.bug_compat:
+        raise ValueError(f"{who} integrates (bug_compat=True would return the inputs every segment)")
+    _graph_source(k, r_cut, edges, who)
+    B = int(batch_size)
+    if loc.dim() != 2 or loc.shape[1] != 3 or loc.shape != vel.shape or B < 1 or loc.shape[0] % B:
+        raise ValueError(f"{who}: loc, vel must be [BN, 3] with BN a multiple of batch_size={B}, got "
+                         f"{tuple(loc.shape)}, {tuple(vel.shape)}")
+    steps = list(num_steps) if isinstance(num_steps, (list, tuple)) else [int(num_steps)] * traj_len
+    if len(steps) != traj_len:
+        raise ValueError("num_steps should be a list of length traj_len")
+    _lib.require_device(loc, vel, charges, model.embedding.weight)
+    N = loc.shape[0] // B
+    if isinstance(edges, _graph.NeighborGraph):
+        edges = edges.with_sender_csr()   # (a graph that came out of a rollout)
+    preds, graphs = [], []
+    x, v = loc, vel
+    for T in steps:
+        x, v, edge_attr, nodes, _, g = prepare_inputs_graph(x.reshape(B, N, 3), v.reshape(B, N, 3), N, charges,
+                                                            k=k, r_cut=r_cut, edges=edges, tape=True)
+        graphs.append(g)
+        x, _, v = model(nodes[:, :1].detach(), x, g, v, edge_attr.detach(), T=int(T))
+        preds.append(x)
+    preds = torch.stack(preds)
+    return (preds, graphs) if return_graphs else preds

@@ -12,7 +12,9 @@ Training (train_nbody.py:168-179): in train mode with gradients enabled, forward
 autograd.SEGNOTrain: the embedding Linear (nonode_embedding_forward / _backward) and the HIP
 integrator forward with saved substeps and its hand-written reverse pass, so loss.backward() reaches
 every parameter. forward_step (an already-embedded h) and several inputs go through
-autograd.SEGNOStepTrain with the embedding as torch ops on the tape.
+autograd.SEGNOStepTrain with the embedding as torch ops on the tape. On an edge list that is not the full
+one, SEGNO(graph="any", trainable=True) trains through autograd.SEGNOGraphTrain / SEGNOGraphStepTrain (the CSR
+graph kernels and their reverse, csrc/nonode_graph_train.hip).
 """
 import ctypes
 
@@ -60,15 +62,30 @@ class SEGNO(nn.Module):
     graph (keyword, not in the reference, like bug_compat): "full" (default) takes exactly the dataset's
     fully connected, equal-size batch; "any" also takes every other edge list (inference only) on the
     CSR graph kernels (csrc/nonode_graph.hip), while a list already known to be full keeps the fused path.
+
+    trainable (keyword, default False; needs graph="any"): a taped forward (training, or an input that
+    requires grad), a taped forward_step and the multi-input forward ('sum' / 'attn') on a list not known to
+    be full run the general-graph training path: autograd.SEGNOGraphTrain / SEGNOGraphStepTrain, one node of
+    the tape per forward_step that saves T * n * 266 floats (about 1.4 GB at n = 25,600 nodes and 50
+    substeps) and reverses the substeps on the CSR by receiver and by sender. `edges` may then be a
+    graph.NeighborGraph that carries its CSR by sender (graph.neighbor_graph(by_sender=True) /
+    with_sender_csr()): edge_attr is [capacity, in_edge_nf] and nothing reads the edge count back. No gradient
+    for edge_attr (pass it detached) and none through the choice of neighbours. Without the keyword nothing
+    changes: graph="any" keeps refusing a taped forward on a general list ("inference only"), and the value
+    graph="trainable" (EGNO's spelling) stays refused here.
     """
 
     def __init__(self, in_node_nf, in_edge_nf, hidden_nf, device='cpu', act_fn=nn.SiLU(), n_layers=4,
                  coords_weight=1.0, recurrent=False, norm_diff=False, tanh=False, invariant=True,
-                 norm_vel=True, varDT=False, multiple_agg=None, bug_compat=False, *, graph="full"):
+                 norm_vel=True, varDT=False, multiple_agg=None, bug_compat=False, *, graph="full", trainable=False):
         super().__init__()
         if graph not in ("full", "any"):
             raise ValueError(f'graph must be "full" or "any", got {graph!r}')
+        if trainable and graph != "any":
+            raise ValueError('trainable=True trains on general edge lists: it needs graph="any" '
+                             f'(graph={graph!r} takes the fully connected list alone, which always trains)')
         self.graph = graph
+        self.trainable = bool(trainable)
         unsupported = []
         if hidden_nf != 64:
             unsupported.append(f"hidden_nf={hidden_nf}")
@@ -177,7 +194,13 @@ class SEGNO(nn.Module):
         if self.bug_compat:
             # the live reference forward returns its inputs (and the embedded h)
             return x, self._embed(his), v
-        if self._tapes(his, x, v) and not self._general(edges, x.shape[0], True):
+        if self._tapes(his, x, v) and self._general(edges, x.shape[0], True, (his, x, v, edge_attr)):
+            if his.shape[-1] > 40:   # (as below)
+                return self._step(self._embed(his), x, edges, v, edge_attr, int(T), tape=True)
+            from .autograd import segno_graph_train
+            g = self._train_graph(x, edges, edge_attr)
+            return finish(segno_graph_train(self, his, x, v, edge_attr, int(T), g))
+        if self._tapes(his, x, v):
             if his.shape[-1] > 40:   # (nonode_embedding_* take up to 40 input features)
                 return self._step(self._embed(his), x, edges, v, edge_attr, int(T), tape=True)
             # the embedding and the T substeps as one autograd node (autograd.SEGNOTrain)
@@ -198,6 +221,8 @@ class SEGNO(nn.Module):
             raise ValueError("SEGNO with several inputs needs in_steps (train_nbody.py:114)")
         if his.dim() != 3 or v.dim() != 3 or his.shape[1] != x.shape[1] or v.shape[1] != x.shape[1]:
             raise ValueError("his, x, v must be [BN, I, .] with the same I")
+        if self.trainable and self._training():   # the taped general path's refusals, in their order
+            self._general(edges, x.shape[0], True, (his, x, v, edge_attr))
         _lib.require_device(his, x, v, edge_attr, self.embedding.weight)
         st = in_steps.tolist() if torch.is_tensor(in_steps) else list(in_steps)
         steps = [int(b) - int(a) for a, b in zip(st[:-1], st[1:])] + [int(T)]
@@ -231,8 +256,12 @@ class SEGNO(nn.Module):
         """forward_step from an embedded h: on the autograd tape in training (tape: the caller's own
         decision, the single-input forms' _tapes), else the fused inference launch."""
         tape = self._training() if tape is None else tape
-        if not tape or self._general(edges, x.shape[0], tape):
+        if not tape:
             return self._run(None, h, x, edges, v, edge_attr, T)
+        if self._general(edges, x.shape[0], True, (h, x, v, edge_attr)):
+            from .autograd import segno_graph_step_train
+            g = self._train_graph(x, edges, edge_attr)
+            return finish(segno_graph_step_train(self, h, x, v, edge_attr, T, g))
         _lib.require_device(h)
         B, N = self._check_inputs(x, edges, v, edge_attr)
         from .autograd import segno_step_train
@@ -261,15 +290,40 @@ class SEGNO(nn.Module):
             out = out + x[..., k:k + 1] * w[:, k]
         return out
 
-    def _general(self, edges, n_nodes, tapes):
+    def _general(self, edges, n_nodes, tapes, inputs=()):
         """Whether this call takes the general-graph path (graph="any" and an edge list not already
-        known to be the fully connected one). Inference only: refused before any device work otherwise."""
+        known to be the fully connected one). Without trainable=True it is inference only: a taped call is
+        refused before any device work. With it, a taped call's refusals come in EGNO's order: an edge_attr
+        that requires grad, a NeighborGraph without its CSR by sender, the device check, the host list's
+        index range."""
         if self.graph != "any" or _graph.known_full(edges, n_nodes) is not None:
             return False
         if tapes:
-            raise NotImplementedError("general graphs: inference only")
+            if not self.trainable:
+                raise NotImplementedError("general graphs: inference only")
+            edge_attr = inputs[-1] if inputs else None
+            if torch.is_grad_enabled() and edge_attr is not None and edge_attr.requires_grad:
+                raise NotImplementedError(
+                    "SEGNO on a general graph has no gradient for edge_attr: the reference detaches it "
+                    "(train_nbody.py:123,233) and the per-edge input gradient is not built; pass edge_attr.detach()")
+            if isinstance(edges, _graph.NeighborGraph) and not edges.has_sender_csr():
+                raise NotImplementedError(
+                    "SEGNO(trainable=True) does not train on a NeighborGraph without its CSR by sender, which the "
+                    "reverse pass walks: build the graph with graph.neighbor_graph(..., by_sender=True) or pass "
+                    "ng.with_sender_csr(); or train on its compacted list, edges = ng.edge_index() (which "
+                    "synchronises), with edge_attr[:E]")
+            _lib.require_device(*inputs, self.embedding.weight)
         _graph.check_host_range(edges, n_nodes)
         return True
+
+    def _train_graph(self, x, edges, edge_attr):
+        """(n, E, csr by receiver, csr by sender + mask) of a taped call on a general list, after the shape
+        check (a NeighborGraph: E = its capacity)."""
+        n = x.shape[0]
+        E = _graph._split(edges)[0].numel()
+        if edge_attr.shape != (E, self.in_edge_nf):
+            raise ValueError(f"edge_attr must be [{E}, {self.in_edge_nf}]")
+        return n, E, _graph.csr(edges, n, device=x.device), _graph.csr_by_sender(edges, n, device=x.device)
 
     @torch.no_grad()
     def _run_graph(self, his, h_in, x, edges, v, edge_attr, T):

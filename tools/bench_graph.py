@@ -1,7 +1,7 @@
 """Timings of the general-graph path (EGNO graph="any", csrc/nonode_graph.hip) on the GPU. One JSON
 line per case on stdout (DESIGN.md section 3.7 quotes them; raw lines under profiles/graph/).
 
-python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|knn_rollout_train|all] [--reps 7] [--iters 20] [--arm both|ours]
+python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|knn_rollout_train|segno_train|all] [--reps 7] [--iters 20] [--arm both|ours]
 
   price  the C2 graph (B = 512, N = 20, T = 10: 5120 fully connected graphs per layer launch) through
          the fused layer entry (nonode_egnn_layer) and, passed as an edge list, through the general one
@@ -29,6 +29,11 @@ python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|knn_rollout_
          ng.edge_index() (one host synchronisation), edge_fea[:E], a taped forward on the compacted list (both
          CSRs through graph.csr / graph.csr_by_sender's cached-list builds) and the frame choice and loc_mean as
          torch ops on the tape, alternated likewise. --arm ours runs the first arm alone.
+  segno_train  SEGNO trained on the knn graph: 8 graphs x 1000 nodes, k = 16 (the device-built NeighborGraph with its
+         CSR by sender, edge_attr [capacity, 2]), T = 10 substeps, one forward + backward of
+         SEGNO(graph="any", trainable=True).train() (MSE on x; every live parameter's gradient) against fp32 autograd
+         of oracle/torch_ref.segno_forward_step (dense_mean=False) on the graph's list on the same device, alternated
+         likewise. --arm ours runs the HIP arm alone.
 Times are device events around `iters` back-to-back calls after a warm-up; each case reports the median
 over the reps and the spread (min, max) beside it.
 """
@@ -383,17 +388,67 @@ def case_knn_rollout_train(args):
     return res
 
 
+def case_segno_train(args):
+    B, N, T, K = 8, 1000, 10, 16
+    torch.manual_seed(0)
+    m = pkg.SEGNO(in_node_nf=1, in_edge_nf=2, hidden_nf=64, n_layers=8, recurrent=True, device=DEV, graph="any",
+                  trainable=True).train()
+    loc, vel, q = synthetic(B, N, 2)
+    x, v, ea, nodes, _, ng = harness.prepare_inputs_graph(loc, vel, N, q, k=K, tape=True)
+    his = nodes[:, :1].contiguous()
+    rows, cols = ng.edge_index()          # (reads the edge count once, outside the timed region: the torch arm's list)
+    E = rows.numel()
+    ea_list = ea[:E].contiguous()
+    target = x + 0.1
+    p32 = {k_: t.detach().float().clone().requires_grad_(True) for k_, t in m.state_dict().items()}
+
+    def ours():
+        m.zero_grad(set_to_none=True)
+        xo, _, _ = m(his, x, ng, v, ea, T=T)
+        ((xo - target) ** 2).mean().backward()
+
+    def ref():
+        for t in p32.values():
+            t.grad = None
+        with torch.device(DEV):   # (torch_ref's factory calls take the default device)
+            xo, _, _ = tr.segno_forward_step(p32, his, x, rows, cols, v, ea_list, T=T, dense_mean=False)
+        ((xo - target) ** 2).mean().backward()
+
+    arms = {"trainable": ours} if args.arm == "ours" else {"trainable": ours, "torch_ref": ref}
+    t = alternate(arms, args.reps, max(args.iters // 4, 3))
+    g = stats(t["trainable"])
+    res = {"case": "segno_train", "shape": {"graphs": B, "nodes_per_graph": N, "k": K, "T": T, "E": E,
+                                            "capacity": ng.capacity},
+           "trainable_fwd_bwd": g, "trainable_per_rep_ms": t["trainable"],
+           "substep_groups": len(autograd.graph_frame_groups(T, ng.capacity)),
+           "state_bytes": int(pkg.lib().nonode_segno_graph_train_state_bytes(B * N, T))}
+    if args.arm != "ours":
+        r = stats(t["torch_ref"])
+        ours()
+        ref()
+        torch.cuda.synchronize()
+        gerr = {k_: float((q_.grad - p32[k_].grad).abs().max() / p32[k_].grad.abs().max())
+                for k_, q_ in m.named_parameters()
+                if q_.grad is not None and p32[k_].grad is not None and float(p32[k_].grad.abs().max()) > 0}
+        res.update({"torch_ref_fp32_fwd_bwd": r, "torch_ref_per_rep_ms": t["torch_ref"],
+                    "speedup_over_torch_ref": r["median_ms"] / g["median_ms"],
+                    "speedup_per_rep": [b_ / a_ for a_, b_ in zip(t["trainable"], t["torch_ref"])],
+                    "worst_grad_maxnorm_rel_vs_torch_ref_fp32": max(gerr.values()), "grads_compared": len(gerr)})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", default="all", choices=["price", "knn", "knn_train", "knn_rollout", "knn_rollout_train", "all"])
-    ap.add_argument("--arm", default="both", choices=["both", "ours"], help="knn_train, knn_rollout, knn_rollout_train: the HIP arm alone")
+    ap.add_argument("--case", default="all", choices=["price", "knn", "knn_train", "knn_rollout", "knn_rollout_train", "segno_train", "all"])
+    ap.add_argument("--arm", default="both", choices=["both", "ours"], help="knn_train, knn_rollout, knn_rollout_train, segno_train: the HIP arm alone")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_graph.py measures on the GPU: no ROCm device found")
     for name, fn in (("price", case_price), ("knn", case_knn), ("knn_train", case_knn_train),
-                     ("knn_rollout", case_knn_rollout), ("knn_rollout_train", case_knn_rollout_train)):
+                     ("knn_rollout", case_knn_rollout), ("knn_rollout_train", case_knn_rollout_train),
+                     ("segno_train", case_segno_train)):
         if args.case in (name, "all"):
             res = fn(args)
             res["device"] = torch.cuda.get_device_name(0)
