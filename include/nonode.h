@@ -425,6 +425,19 @@ int nonode_prepare_inputs_bwd(int B, int N, int F, const int* t_in, const float*
 int nonode_energy(int kind, int F, int B, int N, const float* loc, const float* vel, const float* weights,
                   float* out, void* stream);
 
+/* nonode_prepare_inputs_bwd for G graphs of mixed sizes (graph_ptr [G + 1], the exclusive prefix sum of the
+ * sizes N_g >= 1 over n_total rows; t_in [G] or NULL): g_x, g_v, g_lm [n_total][3] -> g_loc, g_vel
+ * [F][n_total][3], g_loc[f_g][n] = g_x[n] + (1/N_g) sum_m g_lm[m] over the rows m of n's graph, added in
+ * node order (deterministic), zero in every other frame. */
+int nonode_prepare_inputs_bwd_ragged(int G, int n_total, int F, const int* graph_ptr, const int* t_in,
+                                     const float* g_x, const float* g_v, const float* g_lm, float* g_loc,
+                                     float* g_vel, void* stream);
+
+/* nonode_energy of F frames x G graphs of mixed sizes (graph_ptr as above): loc, vel [F][n_total][3], weights
+ * [n_total], each energy over the graph's own nodes. out [F][G]. */
+int nonode_energy_ragged(int kind, int F, int G, int n_total, const int* graph_ptr, const float* loc, const float* vel,
+                         const float* weights, float* out, void* stream);
+
 size_t nonode_egno_rollout_workspace_bytes(int B, int N, int T, int Bt, int in_node, int n_edge_feat);
 
 /* rollout_fn (EGNO/main_simulation_simple_no.py:342-384, num_inputs == 1): traj_len segments of
@@ -712,6 +725,28 @@ int nonode_neighbor_graph(int B, int N, int k, float r2_max, const float* x, int
                           int* rows, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * nonode_neighbor_graph for a batch of G graphs of mixed sizes over the n_total rows of x [n_total][3]:
+ * graph g is rows graph_ptr[g] .. graph_ptr[g + 1] (graph_ptr [G + 1], the exclusive prefix sum of the
+ * sizes N_g >= 1, graph_ptr[G] = n_total), graph_of [n_total] names every row's graph, n_max is the largest
+ * N_g (device pointers; the same kernels, which take a graph's bounds from here instead of from a division).
+ * The contract above holds per graph: receiver r of graph g keeps the min(k, N_g - 1, candidates) nodes
+ * j != r of its own graph with the smallest (d2, j), d2 and the candidates as above, listed by ascending
+ * sender; a graph of one node has rows of degree 0. cap = sum_g N_g min(k, N_g - 1) (the caller's: the host
+ * knows the sizes) is the length of col, rows, eid, with the (-1, -1, p) tail from E = row_ptr[n_total] up
+ * to cap. A pure function of the positions and the sizes, bitwise; equal sizes give nonode_neighbor_graph's
+ * arrays. Refused with NONODE_EINVAL before any launch: G < 1, n_total < G, n_total >= 2^30, n_max outside [1, n_total],
+ * k outside [1, 64], r2_max not > 0, cap < 0, cap >= 2^31, cap > n_total*min(k, n_max - 1), null pointers.
+ * A descriptor that disagrees with cap or n_total cannot make a kernel write outside [0, cap) of col, rows,
+ * eid or [0, n_total] of row_ptr (graph bounds are held to [0, n_total], every store is guarded).
+ * Asynchronous. Workspace: nonode_neighbor_graph_ragged_workspace_bytes(n_total, n_max, k) =
+ * (n_total + n_total*min(k, n_max - 1)) ints (the rows at one fixed pitch); 0 for refused arguments.
+ */
+size_t nonode_neighbor_graph_ragged_workspace_bytes(int n_total, int n_max, int k);
+int nonode_neighbor_graph_ragged(int G, int n_total, int n_max, int k, long long cap, float r2_max,
+                                 const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
+                                 int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The same graph as a CSR by sender, which the reverse pass of the graph layer
  * (nonode_egnn_layer_graph_bwd) walks: what training on a graph rebuilt every step needs, made on the
  * device from the padded list and its device-side count (nonode_graph_build cannot take a list with a
@@ -743,6 +778,16 @@ int nonode_neighbor_by_sender(long long cap, int n_total, const int* rows, const
 int nonode_prepare_nodes(int B, int N, int F, const float* loc, const float* vel, const int* t_in,
                          const float* charges, float* x_out, float* v_out, float* nodes, float* loc_mean,
                          void* stream);
+
+/*
+ * nonode_prepare_nodes for G graphs of mixed sizes (graph_ptr [G + 1] as in nonode_neighbor_graph_ragged): loc,
+ * vel [F][n_total][3], t_in [G] or NULL, charges [n_total] or NULL -> x_out, v_out, loc_mean [n_total][3],
+ * nodes [n_total][1 + (charges != NULL)]. The mean is over the graph's own N_g rows, summed in a fixed tree
+ * that depends on N_g alone: a graph of N rows gets bitwise the mean nonode_prepare_nodes gives it.
+ */
+int nonode_prepare_nodes_ragged(int G, int n_total, int F, const int* graph_ptr, const float* loc, const float* vel,
+                                const int* t_in, const float* charges, float* x_out, float* v_out, float* nodes,
+                                float* loc_mean, void* stream);
 
 /*
  * The edge side on an explicit list (the reference computes these columns only in the full order:

@@ -45,6 +45,8 @@ SYMBOLS = (
     "nonode_neighbor_graph_workspace_bytes", "nonode_neighbor_graph", "nonode_prepare_nodes", "nonode_edge_features",
     "nonode_neighbor_by_sender_workspace_bytes", "nonode_neighbor_by_sender",
     "nonode_segno_graph_train_state_bytes", "nonode_segno_forward_train_graph", "nonode_segno_layer_graph_bwd",
+    "nonode_neighbor_graph_ragged_workspace_bytes", "nonode_neighbor_graph_ragged", "nonode_prepare_nodes_ragged",
+    "nonode_prepare_inputs_bwd_ragged", "nonode_energy_ragged",
 )
 
 VARIANT_EGNO = 0
@@ -268,6 +270,12 @@ def lib():
     L.nonode_neighbor_by_sender.argtypes = [_ll, _i] + [_vp] * 7 + [_sz, _vp]
     L.nonode_prepare_nodes.argtypes = [_i] * 3 + [_vp] * 9
     L.nonode_edge_features.argtypes = [_ll, _i, _vp, _vp, _i] + [_vp] * 5
+    L.nonode_neighbor_graph_ragged_workspace_bytes.argtypes = [_i] * 3
+    L.nonode_neighbor_graph_ragged_workspace_bytes.restype = _sz
+    L.nonode_neighbor_graph_ragged.argtypes = [_i] * 4 + [_ll, _f] + [_vp] * 8 + [_sz, _vp]
+    L.nonode_prepare_nodes_ragged.argtypes = [_i] * 3 + [_vp] * 10
+    L.nonode_prepare_inputs_bwd_ragged.argtypes = [_i] * 3 + [_vp] * 8
+    L.nonode_energy_ragged.argtypes = [_i] * 4 + [_vp] * 6
     L.nonode_profile_begin.argtypes = [_i]
     L.nonode_profile_end.argtypes = [ctypes.POINTER(_f), ctypes.POINTER(_i), _i]
     for s in SYMBOLS:

@@ -695,6 +695,18 @@ __device__ __forceinline__ void mm64_scaled(f4 (&acc)[4], const h8* wh, const f4
   for (int mt = 0; mt < 4; ++mt) acc[mt] += t[mt] * up;
 }
 
+// Rows [r0, r0 + n) of graph b in a batch over n_total rows. graph_ptr null: B graphs of N rows each (b N ..
+// b N + N). Otherwise graphs of mixed sizes, graph b = graph_ptr[b] .. graph_ptr[b + 1], held to [0, n_total]
+// (n <= 0 for a descriptor that is not a prefix sum: the caller's loops then run over nothing).
+struct GraphRows {
+  int r0, n;
+};
+__device__ __forceinline__ GraphRows graph_rows(const int* __restrict__ graph_ptr, int b, int N, int n_total) {
+  if (!graph_ptr) return GraphRows{b * N, N};
+  const int lo = imin(imax(graph_ptr[b], 0), n_total), hi = imin(imax(graph_ptr[b + 1], 0), n_total);
+  return GraphRows{lo, hi - lo};
+}
+
 // packed half2 (2^-k, 2^-k) of an fp16x3 matrix (blob scalar slot SC_H16S + idx, see h8_scale)
 __device__ __forceinline__ unsigned h16_us(const float* scal, int idx) {
   return __float_as_uint(scal[SC_H16S + idx]);

@@ -23,6 +23,10 @@
 //                           by position, so the result is bitwise reproducible
 //   node_features_kernel   the node side of prepare_inputs (frame choice, |v|, q, per-graph mean)
 //   edge_features_kernel    [q_r q_c, |x_r - x_c|^2] per listed edge below a device-side count
+//
+// A batch is B graphs of N consecutive rows, or graphs of mixed sizes named by graph_ptr [G + 1] (the prefix
+// sum of the sizes) and graph_of [n_total] (the *_ragged entries): the same kernels, which take a graph's
+// bounds from graph_rows (nonode_common.h) where the equal-size call divides.
 #include "nonode_common.h"
 
 #pragma clang fp contract(off)
@@ -66,19 +70,33 @@ __device__ __forceinline__ float dist2(float a0, float a1, float a2, float b0, f
   return ((d0 * d0) + (d1 * d1)) + (d2 * d2);
 }
 
-// One wave per receiver r = g N + i. Lane l of `best` holds the l-th smallest key seen so far
-// (ascending). Of a chunk of 64 candidates only the keys below the kk-th best matter (that bound only
-// falls, so a key at or above it never reaches the final kk): none, the chunk is skipped; a few
-// (INSERT_MAX), each is inserted at its rank (one ballot, one lane shift); more, the chunk is sorted
-// and merged in. tmp [B N][kk]: the row's senders (global index) ascending; deg [B N].
+// One wave per receiver r = g0 + i of a graph of N rows from g0 on. Lane l of `best` holds the l-th
+// smallest key seen so far (ascending). Of a chunk of 64 candidates only the keys below the kk-th best
+// matter, kk = min(k, N - 1) (that bound only falls, so a key at or above it never reaches the final kk):
+// none, the chunk is skipped; a few (INSERT_MAX), each is inserted at its rank (one ballot, one lane
+// shift); more, the chunk is sorted and merged in. tmp [n_total][pitch]: the row's senders (global index)
+// ascending; deg [n_total].
+// The receiver's graph: graph_of null, equal sizes (g0 = (r / n_each) n_each, N = n_each); otherwise graph
+// g = graph_of[r] of n_graphs, rows graph_ptr[g] .. graph_ptr[g + 1] (graph_rows holds them to
+// [0, n_total], and kk to the pitch, so nothing below leaves x, tmp or deg whatever the descriptor says).
+// g0, N and kk are the same in every lane and kept in scalar registers.
 constexpr int INSERT_MAX = 8;
-__global__ __launch_bounds__(256) void neighbor_select_kernel(int n_total, int N, int kk, float r2_max,
+__global__ __launch_bounds__(256) void neighbor_select_kernel(int n_total, int n_each, int k, int pitch, float r2_max,
+                                                              int n_graphs, const int* __restrict__ graph_ptr,
+                                                              const int* __restrict__ graph_of,
                                                               const float* __restrict__ x, int* __restrict__ tmp,
                                                               int* __restrict__ deg) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= n_total) return;   // (wave-uniform)
-  const int g0 = (r / N) * N, i = r - g0;
+  GraphRows gr{(r / n_each) * n_each, n_each};
+  if (graph_of) gr = graph_rows(graph_ptr, imin(imax(graph_of[r], 0), n_graphs - 1), 0, n_total);
+  const int g0 = __builtin_amdgcn_readfirstlane(gr.r0), N = __builtin_amdgcn_readfirstlane(gr.n);
+  const int kk = imin(imin(k, N - 1), pitch), i = r - g0;
+  if (kk <= 0) {   // a graph of one node: no pair (wave-uniform)
+    if (lane == 0) deg[r] = 0;
+    return;
+  }
   const float xi0 = x[(size_t)r * 3 + 0], xi1 = x[(size_t)r * 3 + 1], xi2 = x[(size_t)r * 3 + 2];
   u64 best = KEY_NONE;
   for (int base = 0; base < N; base += 64) {
@@ -114,37 +132,41 @@ __global__ __launch_bounds__(256) void neighbor_select_kernel(int n_total, int N
   // the kept senders by ascending index (the sentinel sorts last)
   u64 byj = kept ? (u64)(unsigned)best : KEY_NONE;
   byj = bitonic_sort(byj, lane);
-  if (lane < d) tmp[(size_t)r * kk + lane] = g0 + (int)(unsigned)byj;
+  if (lane < d) tmp[(size_t)r * pitch + lane] = g0 + (int)(unsigned)byj;
   if (lane == 0) deg[r] = d;
 }
 
-// thread t = r kk + l: entry l of row r moves to row_ptr[r] + l; position t of the outputs, when it is
-// at or past the edge count, gets the tail's (-1, -1, t)
-__global__ __launch_bounds__(256) void neighbor_compact_kernel(long long cap, int n_total, int kk,
+// thread t = r pitch + l of the n_total pitch fixed-pitch slots: entry l of row r moves to row_ptr[r] + l;
+// position t of the outputs, when it is at or past the edge count, gets the tail's (-1, -1, t). The
+// outputs hold cap <= n_total pitch entries (equal sizes: cap = n_total pitch) and no store leaves [0, cap).
+__global__ __launch_bounds__(256) void neighbor_compact_kernel(long long cap, int n_total, int pitch,
                                                                const int* __restrict__ row_ptr,
                                                                const int* __restrict__ tmp, int* __restrict__ col,
                                                                int* __restrict__ eid, int* __restrict__ rows) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= cap) return;
-  const int r = (int)(t / kk), l = (int)(t - (long long)r * kk);
+  if (t >= (long long)n_total * pitch) return;
+  const int r = (int)(t / pitch), l = (int)(t - (long long)r * pitch);
   const int p0 = row_ptr[r], d = row_ptr[r + 1] - p0;
-  if (l < d) {
-    const int p = p0 + l;
+  const long long p = (long long)p0 + l;
+  if (l < d && p >= 0 && p < cap) {
     col[p] = tmp[t];
     rows[p] = r;
-    eid[p] = p;
+    eid[p] = (int)p;
   }
-  if (t >= row_ptr[n_total]) {
+  if (t >= row_ptr[n_total] && t < cap) {
     col[t] = -1;
     rows[t] = -1;
     eid[t] = (int)t;
   }
 }
 
-// The node side of prepare_inputs, one 256-thread block per graph: frame t_in[b] - 1 (python index;
-// null: the last frame) of loc, vel [F][B N][3] -> x, v [B N][3], nodes = [|v|] or [|v|, q], loc_mean
-// [B N][3]. The mean's sum is a fixed tree (per-thread strided partial sums, then halving in LDS).
-__global__ __launch_bounds__(256) void node_features_kernel(int B, int N, int F, const float* __restrict__ loc,
+// The node side of prepare_inputs, one 256-thread block per graph (graph_rows: N rows each, or the batch's
+// own graph_ptr): frame t_in[b] - 1 (python index; null: the last frame) of loc, vel [F][n_total][3] ->
+// x, v [n_total][3], nodes = [|v|] or [|v|, q], loc_mean [n_total][3]. The mean's sum is a fixed tree
+// (per-thread strided partial sums, then halving in LDS) that depends on the graph's size alone.
+__global__ __launch_bounds__(256) void node_features_kernel(int n_total, int n_each, int F,
+                                                            const int* __restrict__ graph_ptr,
+                                                            const float* __restrict__ loc,
                                                             const float* __restrict__ vel, const int* __restrict__ t_in,
                                                             const float* __restrict__ q, float* __restrict__ x_out,
                                                             float* __restrict__ v_out, float* __restrict__ nodes,
@@ -153,7 +175,9 @@ __global__ __launch_bounds__(256) void node_features_kernel(int B, int N, int F,
   const int b = blockIdx.x, tid = threadIdx.x;
   int f = F - 1;
   if (t_in) f = ((t_in[b] - 1) % F + F) % F;
-  const size_t BN = (size_t)B * N, r0 = (size_t)b * N;
+  const GraphRows gr = graph_rows(graph_ptr, b, n_each, n_total);
+  const int N = gr.n;
+  const size_t BN = (size_t)n_total, r0 = (size_t)gr.r0;
   const float* lf = loc + ((size_t)f * BN + r0) * 3;
   const float* vf = vel + ((size_t)f * BN + r0) * 3;
   const int nn = q ? 2 : 1;
@@ -263,6 +287,38 @@ __global__ __launch_bounds__(256) void sender_sort_kernel(int n_total, const int
 
 long long neighbor_capacity(int B, int N, int k) { return (long long)B * N * (k < N - 1 ? k : N - 1); }
 
+// The builder's launches for a batch over n_total rows whose largest graph has n_max: the workspace rows
+// at the fixed pitch min(k, n_max - 1), the outputs with cap entries. graph_of null: equal sizes, every
+// graph n_max rows (cap = n_total pitch); otherwise the n_graphs graphs graph_ptr / graph_of name.
+int launch_neighbor_graph(const char* who, int n_total, int n_max, int k, long long cap, float r2_max, int n_graphs,
+                          const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col, int* eid,
+                          int* rows, void* workspace, hipStream_t s) {
+  const int pitch = k < n_max - 1 ? k : n_max - 1;
+  int* deg = (int*)workspace;
+  int* tmp = deg + n_total;
+  if (pitch == 0) {   // graphs of one node: no pair at all
+    if (hipMemsetAsync(row_ptr, 0, ((size_t)n_total + 1) * sizeof(int), s) != hipSuccess)
+      return fail(NONODE_ELAUNCH, "%s: memset", who);
+    return NONODE_OK;
+  }
+  hipLaunchKernelGGL(neighbor_select_kernel, dim3((n_total + 3) / 4), dim3(256), 0, s, n_total, n_max, k, pitch, r2_max,
+                     n_graphs, graph_ptr, graph_of, x, tmp, deg);
+  if (int rc = check_launch("neighbor_select_kernel")) return rc;
+  if (int rc = nonode_tu::graph_scan(n_total, deg, row_ptr, s)) return rc;
+  const long long slots = (long long)n_total * pitch;
+  hipLaunchKernelGGL(neighbor_compact_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, cap, n_total,
+                     pitch, row_ptr, tmp, col, eid, rows);
+  return check_launch("neighbor_compact_kernel");
+}
+
+int launch_node_features(int n_graphs, int n_total, int n_each, int F, const int* graph_ptr, const float* loc,
+                         const float* vel, const int* t_in, const float* charges, float* x_out, float* v_out,
+                         float* nodes, float* loc_mean, hipStream_t s) {
+  hipLaunchKernelGGL(node_features_kernel, dim3(n_graphs), dim3(256), 0, s, n_total, n_each, F, graph_ptr, loc, vel,
+                     t_in, charges, x_out, v_out, nodes, loc_mean);
+  return check_launch("node_features_kernel");
+}
+
 }  // namespace
 
 extern "C" {
@@ -285,22 +341,31 @@ int nonode_neighbor_graph(int B, int N, int k, float r2_max, const float* x, int
   if (workspace_bytes < nonode_neighbor_graph_workspace_bytes(B, N, k))
     return fail(NONODE_EINVAL, "neighbor_graph: workspace %zu < %zu", workspace_bytes,
                 nonode_neighbor_graph_workspace_bytes(B, N, k));
-  hipStream_t s = (hipStream_t)stream;
-  const int n_total = B * N, kk = k < N - 1 ? k : N - 1;
-  int* deg = (int*)workspace;
-  int* tmp = deg + n_total;
-  if (kk == 0) {   // N = 1: no pair at all
-    if (hipMemsetAsync(row_ptr, 0, ((size_t)n_total + 1) * sizeof(int), s) != hipSuccess)
-      return fail(NONODE_ELAUNCH, "neighbor_graph: memset");
-    return NONODE_OK;
-  }
-  hipLaunchKernelGGL(neighbor_select_kernel, dim3((n_total + 3) / 4), dim3(256), 0, s, n_total, N, kk, r2_max, x, tmp,
-                     deg);
-  if (int rc = check_launch("neighbor_select_kernel")) return rc;
-  if (int rc = nonode_tu::graph_scan(n_total, deg, row_ptr, s)) return rc;
-  hipLaunchKernelGGL(neighbor_compact_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, cap, n_total, kk,
-                     row_ptr, tmp, col, eid, rows);
-  return check_launch("neighbor_compact_kernel");
+  return launch_neighbor_graph("neighbor_graph", B * N, N, k, cap, r2_max, B, nullptr, nullptr, x, row_ptr, col, eid,
+                               rows, workspace, (hipStream_t)stream);
+}
+
+size_t nonode_neighbor_graph_ragged_workspace_bytes(int n_total, int n_max, int k) {
+  if (n_total <= 0 || n_max <= 0 || n_max > n_total || k < 1 || k > 64) return 0;
+  // the degrees, the rows at the fixed pitch min(k, n_max - 1)
+  return ((size_t)n_total + (size_t)n_total * (k < n_max - 1 ? k : n_max - 1)) * sizeof(int);
+}
+
+int nonode_neighbor_graph_ragged(int G, int n_total, int n_max, int k, long long cap, float r2_max,
+                                 const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
+                                 int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream) {
+  if (G < 1 || n_total < G || n_total >= (1 << 30) || n_max < 1 || n_max > n_total || k < 1 || k > 64 ||
+      !(r2_max > 0.f) || cap < 0 || cap >= (1ll << 31) ||
+      cap > (long long)n_total * (k < n_max - 1 ? k : n_max - 1))
+    return fail(NONODE_EINVAL, "neighbor_graph_ragged: G=%d n_total=%d n_max=%d k=%d cap=%lld r2_max=%g (k in [1, 64], "
+                "r2_max > 0, cap <= n_total min(k, n_max - 1))", G, n_total, n_max, k, cap, (double)r2_max);
+  if (!graph_ptr || !graph_of || !x || !row_ptr || !workspace || (cap > 0 && (!col || !eid || !rows)))
+    return fail(NONODE_EINVAL, "neighbor_graph_ragged: null pointer");
+  if (workspace_bytes < nonode_neighbor_graph_ragged_workspace_bytes(n_total, n_max, k))
+    return fail(NONODE_EINVAL, "neighbor_graph_ragged: workspace %zu < %zu", workspace_bytes,
+                nonode_neighbor_graph_ragged_workspace_bytes(n_total, n_max, k));
+  return launch_neighbor_graph("neighbor_graph_ragged", n_total, n_max, k, cap, r2_max, G, graph_ptr, graph_of, x,
+                               row_ptr, col, eid, rows, workspace, (hipStream_t)stream);
 }
 
 size_t nonode_neighbor_by_sender_workspace_bytes(long long cap, int n_total) {
@@ -346,9 +411,19 @@ int nonode_prepare_nodes(int B, int N, int F, const float* loc, const float* vel
   if (B <= 0 || N <= 0 || F <= 0 || (long long)F * B * N >= (1ll << 30))
     return fail(NONODE_EINVAL, "prepare_nodes: B=%d N=%d F=%d", B, N, F);
   if (!loc || !vel || !x_out || !v_out || !nodes) return fail(NONODE_EINVAL, "prepare_nodes: null pointer");
-  hipLaunchKernelGGL(node_features_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, B, N, F, loc, vel, t_in,
-                     charges, x_out, v_out, nodes, loc_mean);
-  return check_launch("node_features_kernel");
+  return launch_node_features(B, B * N, N, F, nullptr, loc, vel, t_in, charges, x_out, v_out, nodes, loc_mean,
+                              (hipStream_t)stream);
+}
+
+int nonode_prepare_nodes_ragged(int G, int n_total, int F, const int* graph_ptr, const float* loc, const float* vel,
+                                const int* t_in, const float* charges, float* x_out, float* v_out, float* nodes,
+                                float* loc_mean, void* stream) {
+  if (G < 1 || n_total < G || F <= 0 || (long long)F * n_total >= (1ll << 30))
+    return fail(NONODE_EINVAL, "prepare_nodes_ragged: G=%d n_total=%d F=%d", G, n_total, F);
+  if (!graph_ptr || !loc || !vel || !x_out || !v_out || !nodes)
+    return fail(NONODE_EINVAL, "prepare_nodes_ragged: null pointer");
+  return launch_node_features(G, n_total, 0, F, graph_ptr, loc, vel, t_in, charges, x_out, v_out, nodes, loc_mean,
+                              (hipStream_t)stream);
 }
 
 int nonode_edge_features(long long cap, int n_nodes, const void* rows, const void* cols, int idx_bytes,

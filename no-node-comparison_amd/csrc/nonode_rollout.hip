@@ -73,14 +73,17 @@ __global__ __launch_bounds__(256) void featurize_kernel(FeatArgs a) {
 // loc_mean; nodes and edge_attr are detached, main_simulation_simple_no.py:321-338). One block per
 // graph: the per-graph mean's gradient (1/N) sum_m g_lm[b][m] added in node order by one thread per
 // coordinate (deterministic), then every frame of the graph written (zero but in the selected frame).
-__global__ __launch_bounds__(256) void featurize_bwd_kernel(int B, int N, int F, const int* t_in, const float* g_x,
-                                                            const float* g_v, const float* g_lm, float* g_loc,
-                                                            float* g_vel) {
+// The graph's rows by graph_rows: N each, or the own bounds (and 1 / N_g) of a batch of mixed sizes.
+__global__ __launch_bounds__(256) void featurize_bwd_kernel(int n_total, int n_each, int F, const int* graph_ptr,
+                                                            const int* t_in, const float* g_x, const float* g_v,
+                                                            const float* g_lm, float* g_loc, float* g_vel) {
   __shared__ float sm[3];
   const int b = blockIdx.x, tid = threadIdx.x;
   int fsel = F - 1;
   if (t_in) fsel = ((t_in[b] - 1) % F + F) % F;
-  const size_t BN = (size_t)B * N, r0 = (size_t)b * N;
+  const GraphRows gr = graph_rows(graph_ptr, b, n_each, n_total);
+  const int N = gr.n;
+  const size_t BN = (size_t)n_total, r0 = (size_t)gr.r0;
   if (tid < 3) {
     float m = 0.f;
     if (g_lm)
@@ -97,19 +100,23 @@ __global__ __launch_bounds__(256) void featurize_bwd_kernel(int B, int N, int F,
   }
 }
 
-// Energy of F frames x B graphs: one wave per (frame, graph), lanes over receivers i, f64 sums.
+// Energy of F frames x B graphs: one wave per (frame, graph), lanes over receivers i of the graph's own rows
+// (graph_rows: N each, or the bounds of a batch of mixed sizes), f64 sums.
 //   kind 0 (charged): 0.5 sum |v|^2 + 0.5 sum_{i != j} q_i q_j / |x_i - x_j|   (0 where the distance is 0)
 //   kind 1 (gravity): 0.5 sum m |v|^2 - sum_{i < j} m_i m_j / |x_i - x_j|      (G = 1)
-__global__ __launch_bounds__(256) void energy_kernel(int kind, int F, int B, int N, const float* loc, const float* vel,
+__global__ __launch_bounds__(256) void energy_kernel(int kind, int F, int B, long long n_total, int n_each,
+                                                     const int* graph_ptr, const float* loc, const float* vel,
                                                      const float* w, float* out) {
   const int lane = threadIdx.x & 63;
   const long long job = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (job >= (long long)F * B) return;
   const int f = (int)(job / B), b = (int)(job - (long long)f * B);
-  const size_t BN = (size_t)B * N;
-  const float* lf = loc + ((size_t)f * BN + (size_t)b * N) * 3;
-  const float* vf = vel + ((size_t)f * BN + (size_t)b * N) * 3;
-  const float* wb = w + (size_t)b * N;
+  const GraphRows gr = graph_rows(graph_ptr, b, n_each, (int)n_total);   // (n_total < 2^30 with a graph_ptr)
+  const int N = gr.n;
+  const size_t BN = (size_t)n_total;
+  const float* lf = loc + ((size_t)f * BN + (size_t)gr.r0) * 3;
+  const float* vf = vel + ((size_t)f * BN + (size_t)gr.r0) * 3;
+  const float* wb = w + (size_t)gr.r0;
   double K = 0.0, U = 0.0;
   for (int i = lane; i < N; i += 64) {
     const double xi0 = lf[i * 3 + 0], xi1 = lf[i * 3 + 1], xi2 = lf[i * 3 + 2];
@@ -179,13 +186,23 @@ int launch_featurize(const FeatArgs& a, hipStream_t s) {
   return check_launch("featurize_kernel");
 }
 
+// graph_ptr null: B graphs of N rows; otherwise the B graphs graph_ptr names over n_total rows (N unused)
 int launch_energy(int kind, int F, int B, int N, const float* loc, const float* vel, const float* w, float* out,
-                  hipStream_t s) {
+                  hipStream_t s, const int* graph_ptr = nullptr, int n_total = 0) {
   if (kind != 0 && kind != 1) return fail(NONODE_EINVAL, "energy: kind=%d", kind);
   const long long jobs = (long long)F * B;
-  hipLaunchKernelGGL(energy_kernel, dim3((unsigned)((jobs + 3) / 4)), dim3(256), 0, s, kind, F, B, N, loc, vel, w,
-                     out);
+  hipLaunchKernelGGL(energy_kernel, dim3((unsigned)((jobs + 3) / 4)), dim3(256), 0, s, kind, F, B,
+                     graph_ptr ? (long long)n_total : (long long)B * N, N, graph_ptr, loc, vel, w, out);
   return check_launch("energy_kernel");
+}
+
+int launch_featurize_bwd(int n_graphs, int n_total, int n_each, int F, const int* graph_ptr, const int* t_in,
+                         const float* g_x, const float* g_v, const float* g_lm, float* g_loc, float* g_vel,
+                         hipStream_t s) {
+  if (!g_loc && !g_vel) return NONODE_OK;
+  hipLaunchKernelGGL(featurize_bwd_kernel, dim3(n_graphs), dim3(256), 0, s, n_total, n_each, F, graph_ptr, t_in, g_x,
+                     g_v, g_lm, g_loc, g_vel);
+  return check_launch("featurize_bwd_kernel");
 }
 
 struct EgnoRolloutWs {
@@ -241,10 +258,16 @@ int nonode_prepare_inputs_bwd(int B, int N, int F, const int* t_in, const float*
                               const float* g_lm, float* g_loc, float* g_vel, void* stream) {
   if (B <= 0 || N < 2 || F <= 0 || (long long)F * N * 3 >= (1ll << 31))
     return fail(NONODE_EINVAL, "prepare_inputs_bwd: B=%d N=%d F=%d", B, N, F);
-  if (!g_loc && !g_vel) return NONODE_OK;
-  hipLaunchKernelGGL(featurize_bwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, B, N, F, t_in, g_x, g_v, g_lm,
-                     g_loc, g_vel);
-  return check_launch("featurize_bwd_kernel");
+  return launch_featurize_bwd(B, B * N, N, F, nullptr, t_in, g_x, g_v, g_lm, g_loc, g_vel, (hipStream_t)stream);
+}
+
+int nonode_prepare_inputs_bwd_ragged(int G, int n_total, int F, const int* graph_ptr, const int* t_in,
+                                     const float* g_x, const float* g_v, const float* g_lm, float* g_loc,
+                                     float* g_vel, void* stream) {
+  if (G < 1 || n_total < G || F <= 0 || (long long)F * n_total * 3 >= (1ll << 31))
+    return fail(NONODE_EINVAL, "prepare_inputs_bwd_ragged: G=%d n_total=%d F=%d", G, n_total, F);
+  if (!graph_ptr) return fail(NONODE_EINVAL, "prepare_inputs_bwd_ragged: null pointer");
+  return launch_featurize_bwd(G, n_total, 0, F, graph_ptr, t_in, g_x, g_v, g_lm, g_loc, g_vel, (hipStream_t)stream);
 }
 
 int nonode_energy(int kind, int F, int B, int N, const float* loc, const float* vel, const float* weights,
@@ -252,6 +275,14 @@ int nonode_energy(int kind, int F, int B, int N, const float* loc, const float* 
   if (F <= 0 || B <= 0 || N < 1) return fail(NONODE_EINVAL, "energy: F=%d B=%d N=%d", F, B, N);
   if (!loc || !vel || !weights || !out) return fail(NONODE_EINVAL, "energy: null pointer");
   return launch_energy(kind, F, B, N, loc, vel, weights, out, (hipStream_t)stream);
+}
+
+int nonode_energy_ragged(int kind, int F, int G, int n_total, const int* graph_ptr, const float* loc, const float* vel,
+                         const float* weights, float* out, void* stream) {
+  if (F <= 0 || G < 1 || n_total < G || (long long)F * n_total >= (1ll << 30))
+    return fail(NONODE_EINVAL, "energy_ragged: F=%d G=%d n_total=%d", F, G, n_total);
+  if (!graph_ptr || !loc || !vel || !weights || !out) return fail(NONODE_EINVAL, "energy_ragged: null pointer");
+  return launch_energy(kind, F, G, 0, loc, vel, weights, out, (hipStream_t)stream, graph_ptr, n_total);
 }
 
 size_t nonode_egno_rollout_workspace_bytes(int B, int N, int T, int Bt, int in_node, int n_edge_feat) {

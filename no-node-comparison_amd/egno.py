@@ -283,6 +283,11 @@ class EGNO(nn.Module):
             raise ValueError("EGNO.forward needs v and loc_mean (the time convolution stacks "
                              "x - loc_mean with v, egno.py:103-105)")
         tapes = self._tapes(x, h, v, loc_mean)
+        if isinstance(edge_index, _graph.NeighborGraph) and edge_index.batch is not None and \
+                timesteps_out is not None and timesteps_out.dim() == 2 and timesteps_out.shape[0] > 1:
+            raise ValueError("EGNO.forward: a NeighborGraph of a batch of mixed sizes takes shared timesteps only "
+                             f"(timesteps_out with one row, got {timesteps_out.shape[0]}): the embedding maps rows "
+                             "of timesteps_out to nodes by equal division")
         if self.graph == "trainable":   # refused before the edge_fea check and before any device work
             if self.flat:
                 raise NotImplementedError('EGNO(graph="trainable") does not run with flat=True')

@@ -34,6 +34,14 @@ segment (harness.egno_rollout_graph / segno_rollout_graph). Built with ``by_send
 made on the device from the padded list (``nonode_neighbor_by_sender``), so EGNO(graph="trainable") and
 SEGNO(graph="any", trainable=True) train on it with nothing read back (harness.egno_rollout_train_graph /
 segno_rollout_train_graph unroll a rollout on such graphs).
+
+Graphs of mixed sizes in one batch (``RaggedBatch``, ``neighbor_graph_ragged``): the descriptor holds the sizes
+on the host and their prefix sum and node -> graph map on the device, uploaded once; the builder, the node
+featuriser, its reverse and the energy kernel read a graph's bounds from it where the equal-size calls divide
+(the same kernels: equal sizes are the degenerate case and give the same bits). The CSR layer kernels need
+nothing else: a mixed batch is just another CSR over n_total nodes, a graph of one node a row of degree 0.
+The NeighborGraph of such a batch has ``n_nodes`` None and ``batch`` set. The embedding kernels map rows of
+``timesteps_out`` to nodes by equal division, so a mixed batch takes shared timesteps (one row) only.
 """
 import math
 import operator
@@ -339,13 +347,17 @@ class NeighborGraph:
     CSR by sender of the reverse pass: ``srow_ptr`` [B N + 1], ``seid`` [capacity] (each sender's positions,
     ascending; -1 at and past the edge count) and ``valid`` [capacity] (1 below the edge count, 0 for the
     tail), all None otherwise. With them EGNO(graph="trainable") and SEGNO(graph="any", trainable=True) train on it
-    (graph.csr_by_sender returns them without a launch); no gradient flows through the choice of neighbours, which is discrete."""
+    (graph.csr_by_sender returns them without a launch); no gradient flows through the choice of neighbours, which is discrete.
 
-    def __init__(self, rows, col, row_ptr, eid, n_nodes, *, srow_ptr=None, seid=None, valid=None):
+    A graph of a batch of mixed sizes (``neighbor_graph_ragged``) has ``n_nodes`` None and ``batch`` its
+    RaggedBatch (None on an equal-size graph); ``capacity`` is then ``batch.capacity(k)``."""
+
+    def __init__(self, rows, col, row_ptr, eid, n_nodes, *, srow_ptr=None, seid=None, valid=None, batch=None):
         self.rows, self.col, self.row_ptr, self.eid = rows, col, row_ptr, eid
         self.capacity = rows.numel()
         self.n_edges = row_ptr[-1:]
         self.n_nodes = n_nodes
+        self.batch = batch
         self.srow_ptr, self.seid, self.valid = srow_ptr, seid, valid
 
     def has_sender_csr(self):
@@ -359,7 +371,7 @@ class NeighborGraph:
             return self
         srow_ptr, seid, valid = _sender_csr(self.rows, self.col, self.row_ptr)
         return NeighborGraph(self.rows, self.col, self.row_ptr, self.eid, self.n_nodes, srow_ptr=srow_ptr,
-                             seid=seid, valid=valid)
+                             seid=seid, valid=valid, batch=self.batch)
 
     def __len__(self):
         return 2
@@ -431,20 +443,110 @@ def neighbor_graph(x, batch_size, n_nodes, k, r_cut=None, *, by_sender=False):
     if B < 1 or N < 1 or x.dim() != 2 or tuple(x.shape) != (B * N, 3):
         raise ValueError(f"neighbor_graph: x must be [batch_size * n_nodes, 3] = [{B * N}, 3], got {tuple(x.shape)}")
     _lib.require_device(x)
+    return _build_neighbor_graph(x, k, r2, by_sender, B, N, None)
+
+
+def _build_neighbor_graph(x, k, r2, by_sender, B, N, batch):
+    """The builder's call behind neighbor_graph (B graphs of N rows; batch None) and neighbor_graph_ragged
+    (batch a RaggedBatch; B, N unused), after their host checks: outputs, workspace, one C call, and the CSR
+    by sender if asked."""
+    from . import _lib
     x = _lib.f32(x)
     dev = x.device
-    cap = B * N * min(k, N - 1)
-    row_ptr = torch.empty(B * N + 1, dtype=torch.int32, device=dev)
+    n_total, cap = (B * N, B * N * min(k, N - 1)) if batch is None else (batch.n_total, batch.capacity(k))
+    row_ptr = torch.empty(n_total + 1, dtype=torch.int32, device=dev)
     col, eid, rows = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
     L = _lib.lib()
-    ws_bytes = L.nonode_neighbor_graph_workspace_bytes(B, N, k)
-    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
-    _lib.check(L.nonode_neighbor_graph(B, N, k, r2, _lib.ptr(x), _lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(eid),
-                                       _lib.ptr(rows), _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
+    out = (_lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(eid), _lib.ptr(rows))
+    if batch is None:
+        ws_bytes = L.nonode_neighbor_graph_workspace_bytes(B, N, k)
+        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+        _lib.check(L.nonode_neighbor_graph(B, N, k, r2, _lib.ptr(x), *out, _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
+    else:
+        ws_bytes = L.nonode_neighbor_graph_ragged_workspace_bytes(n_total, batch.n_max, k)
+        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+        _lib.check(L.nonode_neighbor_graph_ragged(batch.n_graphs, n_total, batch.n_max, k, cap, r2,
+                                                  _lib.ptr(batch.graph_ptr), _lib.ptr(batch.graph_of), _lib.ptr(x),
+                                                  *out, _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
+    n_nodes = N if batch is None else None
     if not by_sender:
-        return NeighborGraph(rows, col, row_ptr, eid, N)
+        return NeighborGraph(rows, col, row_ptr, eid, n_nodes, batch=batch)
     srow_ptr, seid, valid = _sender_csr(rows, col, row_ptr)
-    return NeighborGraph(rows, col, row_ptr, eid, N, srow_ptr=srow_ptr, seid=seid, valid=valid)
+    return NeighborGraph(rows, col, row_ptr, eid, n_nodes, srow_ptr=srow_ptr, seid=seid, valid=valid, batch=batch)
+
+
+class RaggedBatch:
+    """G graphs of mixed sizes in one batch, graph g the N_g consecutive rows from graph_ptr[g] on: what the
+    device-side pieces (neighbor_graph_ragged, harness.prepare_inputs_graph / conserved_energy and the
+    rollout drivers with sizes=) take instead of (batch_size, n_nodes). ``sizes`` is a HOST sequence of ints
+    >= 1 (list, tuple, numpy array or CPU tensor; a device tensor raises ValueError, as reading it would
+    synchronise). Attributes: ``sizes`` (tuple), ``n_graphs``, ``n_total``, ``n_max``, ``graph_ptr`` (int32
+    [G + 1] on `device`, the exclusive prefix sum) and ``graph_of`` (int32 [n_total], node -> graph).
+    Built once, with two small uploads here; everything that takes it reuses it, so a rollout loop uploads
+    nothing and reads nothing back. device="cpu" is allowed (the arithmetic alone)."""
+
+    def __init__(self, sizes, device):
+        if torch.is_tensor(sizes):
+            if sizes.device.type != "cpu":
+                raise ValueError("RaggedBatch: sizes must be on the host (a list, tuple, numpy array or CPU tensor): "
+                                 "reading a device tensor would synchronise")
+            sizes = sizes.reshape(-1).tolist()
+        elif isinstance(sizes, np.ndarray):
+            sizes = sizes.reshape(-1).tolist()
+        try:
+            sizes = tuple(sizes)
+            if any(isinstance(s, bool) for s in sizes):
+                raise TypeError
+            sizes = tuple(operator.index(s) for s in sizes)
+        except TypeError:
+            raise ValueError("RaggedBatch: sizes must be a sequence of ints") from None
+        if not sizes or any(s < 1 for s in sizes):
+            raise ValueError(f"RaggedBatch: sizes must hold at least one graph and every size must be >= 1, got {sizes!r}")
+        if sum(sizes) >= 2 ** 30:
+            raise ValueError(f"RaggedBatch: n_total = {sum(sizes)} (must be < 2^30)")
+        self.sizes = sizes
+        self.n_graphs, self.n_total, self.n_max = len(sizes), sum(sizes), max(sizes)
+        ptr = np.zeros(self.n_graphs + 1, dtype=np.int32)
+        np.cumsum(np.asarray(sizes, dtype=np.int64), out=ptr[1:])
+        of = np.repeat(np.arange(self.n_graphs, dtype=np.int32), sizes)
+        self.graph_ptr = torch.from_numpy(ptr).to(device)
+        self.graph_of = torch.from_numpy(of).to(device)
+        self.device = self.graph_ptr.device
+
+    def capacity(self, k):
+        """sum_g N_g min(k, N_g - 1): the length of a neighbour graph's padded list (host arithmetic)."""
+        return sum(n * min(k, n - 1) for n in self.sizes)
+
+
+def as_batch(sizes, device):
+    """sizes as a RaggedBatch on `device`: itself if it is one (it must live there), else a new one."""
+    if isinstance(sizes, RaggedBatch):
+        if sizes.device != torch.device(device):
+            raise ValueError(f"the RaggedBatch lives on {sizes.device}, the tensors on {device}")
+        return sizes
+    return RaggedBatch(sizes, device)
+
+
+def neighbor_graph_ragged(x, batch, k, r_cut=None, *, by_sender=False):
+    """neighbor_graph for a batch of mixed sizes: x [n_total, 3], batch a RaggedBatch (or a host sequence of
+    sizes, wrapped: repeated callers pass the RaggedBatch). Receiver r of graph g keeps the min(k, N_g - 1,
+    candidates) nodes j != r of its own graph with the smallest (d2, j), d2 and the candidates as in
+    neighbor_graph; a graph of one node has rows of degree 0. One nonode_neighbor_graph_ragged call,
+    asynchronous, nothing read back; bitwise a pure function of the positions and the sizes, and for equal
+    sizes bitwise neighbor_graph's arrays. The NeighborGraph has n_nodes None, batch the descriptor and
+    capacity == batch.capacity(k)."""
+    from . import _lib
+    k, r2 = neighbor_args(k, r_cut)
+    if not isinstance(batch, RaggedBatch):
+        batch = RaggedBatch(batch, x.device)
+    if x.dim() != 2 or tuple(x.shape) != (batch.n_total, 3):
+        raise ValueError(f"neighbor_graph_ragged: x must be [n_total, 3] = [{batch.n_total}, 3], got {tuple(x.shape)}")
+    _lib.require_device(x, batch.graph_ptr)
+    if batch.device != x.device:
+        raise ValueError(f"neighbor_graph_ragged: the RaggedBatch lives on {batch.device}, x on {x.device}")
+    if batch.capacity(k) >= 2 ** 31:
+        raise ValueError(f"neighbor_graph_ragged: capacity {batch.capacity(k)} (must be < 2^31)")
+    return _build_neighbor_graph(x, k, r2, by_sender, 0, 0, batch)
 
 
 # the second CSR of the reverse pass (EGNO graph="trainable"), cached per edge tensor pair like _csr

@@ -9,7 +9,9 @@ Like the models, these have no CPU path: tensors must be on the ROCm device.
 General graphs (models built with graph="any"): prepare_inputs_graph featurises on an explicit edge list,
 and egno_rollout_graph / segno_rollout_graph chain model(...) segments on a k-NN / cut-off graph rebuilt on
 the device from every segment's start (graph.neighbor_graph) or on a fixed list, without a host round trip
-(csrc/nonode_neighbor.hip). The functions above stay full-graph.
+(csrc/nonode_neighbor.hip). The functions above stay full-graph. With sizes= (a graph.RaggedBatch or a host
+sequence of sizes) prepare_inputs_graph, conserved_energy and the four *_rollout*_graph drivers take graphs of
+mixed sizes in one batch, through the same kernels and the same segment loops (_Layout).
 """
 import ctypes
 
@@ -97,16 +99,21 @@ class _PrepareInputs(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gx, gv, glm, _gea, _gnodes):
-        shape = ctx.shape if len(ctx.shape) == 4 else (1,) + ctx.shape
-        F, B, N = shape[0], shape[1], shape[2]
+        batch = getattr(ctx, "batch", None)   # a RaggedBatch (prepare_inputs_graph(sizes=...)): [(F,) n_total, 3]
+        lead = 4 if batch is None else 3
+        shape = ctx.shape if len(ctx.shape) == lead else (1,) + ctx.shape
         ref = next(g for g in (gx, gv, glm) if g is not None)
         dev = ref.device
         gx, gv, glm = _f32(gx), _f32(gv), _f32(glm)
         g_loc = torch.empty(shape, device=dev) if ctx.needs_input_grad[0] else None
         g_vel = torch.empty(shape, device=dev) if ctx.needs_input_grad[1] else None
-        _lib.check(_lib.lib().nonode_prepare_inputs_bwd(B, N, F, _lib.ptr(ctx.ti), _lib.ptr(gx), _lib.ptr(gv),
-                                                        _lib.ptr(glm), _lib.ptr(g_loc), _lib.ptr(g_vel),
-                                                        _lib.stream_of(ref)))
+        grads = (_lib.ptr(ctx.ti), _lib.ptr(gx), _lib.ptr(gv), _lib.ptr(glm), _lib.ptr(g_loc), _lib.ptr(g_vel),
+                 _lib.stream_of(ref))
+        if batch is None:
+            _lib.check(_lib.lib().nonode_prepare_inputs_bwd(shape[1], shape[2], shape[0], *grads))
+        else:
+            _lib.check(_lib.lib().nonode_prepare_inputs_bwd_ragged(batch.n_graphs, batch.n_total, shape[0],
+                                                                   _lib.ptr(batch.graph_ptr), *grads))
         g_loc = g_loc.reshape(ctx.shape).to(ctx.dtypes[0]) if g_loc is not None else None
         g_vel = g_vel.reshape(ctx.shape).to(ctx.dtypes[1]) if g_vel is not None else None
         return g_loc, g_vel, None, None, None, None, None
@@ -161,19 +168,33 @@ def egno_rollout_multi(model, nodes, loc, edges, vel, edge_attr_o, edge_attr, lo
 
 
 @torch.no_grad()
-def conserved_energy(dataset, loc, vel, charges, batch_size):
+def conserved_energy(dataset, loc, vel, charges, batch_size, *, sizes=None):
     """conserved_energy_fun (utils.py:197-219) on the GPU: loc, vel [..., B*N, 3] (leading frame
-    axes allowed), charges (charged) or masses (gravity) [B*N] -> energies [..., B]."""
+    axes allowed), charges (charged) or masses (gravity) [B*N] -> energies [..., B].
+    sizes (a graph.RaggedBatch or a host sequence): G graphs of mixed sizes, loc, vel [..., n_total, 3],
+    charges [n_total] -> [..., G], each energy over the graph's own nodes; batch_size None or len(sizes)."""
+    batch = None
+    if sizes is not None:
+        from .graph import as_batch
+        batch = as_batch(sizes, loc.device)
+        if batch_size is not None and batch_size != batch.n_graphs:
+            raise ValueError(f"conserved_energy: batch_size = {batch_size} with {batch.n_graphs} sizes")
+        if loc.dim() < 2 or loc.shape[-2] != batch.n_total or charges.numel() != batch.n_total:
+            raise ValueError(f"conserved_energy: loc must be [..., {batch.n_total}, 3] and charges hold "
+                             f"{batch.n_total} values, got {tuple(loc.shape)}, {charges.numel()}")
     _lib.require_device(loc, vel, charges)
-    B = batch_size
+    B = batch_size if batch is None else batch.n_graphs
     lead = loc.shape[:-2]
     BN = loc.shape[-2] if loc.dim() >= 2 else loc.numel() // 3
     loc, vel = _f32(loc).reshape(-1, BN, 3), _f32(vel).reshape(-1, BN, 3)
     F, N = loc.shape[0], BN // B
     w = _f32(charges).reshape(-1)
     out = torch.empty(F, B, device=loc.device)
-    _lib.check(_lib.lib().nonode_energy(ENERGY_KIND[dataset], F, B, N, _lib.ptr(loc), _lib.ptr(vel), _lib.ptr(w),
-                                        _lib.ptr(out), _lib.stream_of(loc)))
+    io = (_lib.ptr(loc), _lib.ptr(vel), _lib.ptr(w), _lib.ptr(out), _lib.stream_of(loc))
+    if batch is None:
+        _lib.check(_lib.lib().nonode_energy(ENERGY_KIND[dataset], F, B, N, *io))
+    else:
+        _lib.check(_lib.lib().nonode_energy_ragged(ENERGY_KIND[dataset], F, B, BN, _lib.ptr(batch.graph_ptr), *io))
     return out.reshape(*lead, B) if len(lead) else out.reshape(B)
 
 
@@ -396,7 +417,8 @@ def _graph_source(k, r_cut, edges, who):
         neighbor_args(k, r_cut)
 
 
-def prepare_inputs_graph(loc, vel, n_nodes, charges=None, t_in=None, *, k=None, r_cut=None, edges=None, tape=False):
+def prepare_inputs_graph(loc, vel, n_nodes, charges=None, t_in=None, *, k=None, r_cut=None, edges=None, tape=False,
+                         sizes=None):
     """prepare_inputs (main_simulation_simple_no.py:311-339, num_inputs == 1) on an explicit edge list
     instead of the implicit fully connected one. loc, vel: [B, N, 3] or [F, B, N, 3] with t_in [B] choosing
     frame t_in - 1 per sample (a python index taken modulo F on the device, as nonode_prepare_inputs takes it:
@@ -414,13 +436,24 @@ def prepare_inputs_graph(loc, vel, n_nodes, charges=None, t_in=None, *, k=None, 
     prepare_inputs' own: the selected frame gets g_x + the per-graph mean of g_loc_mean, and g_v; every
     other frame zero). nodes, edge_attr and the graph are not differentiable: the reference detaches the
     first two (main_simulation_simple_no.py:333,338), and the choice of neighbours is discrete, built from
-    the detached positions, so no gradient flows through it."""
+    the detached positions, so no gradient flows through it.
+
+    sizes (a graph.RaggedBatch, or a host sequence of sizes, wrapped; n_nodes must then be None): G graphs of
+    mixed sizes. loc, vel [n_total, 3] or [F, n_total, 3], t_in one value per graph, charges n_total values;
+    the mean is each graph's own, k builds through graph.neighbor_graph_ragged, and the tape's reverse is
+    nonode_prepare_inputs_bwd_ragged. Same returns."""
+    batch = None
+    if sizes is not None:
+        if n_nodes is not None:
+            raise ValueError("prepare_inputs_graph: give n_nodes (equal sizes) or sizes (mixed sizes), not both")
+        from .graph import as_batch
+        batch = as_batch(sizes, loc.device)
     if tape and torch.is_grad_enabled() and (loc.requires_grad or vel.requires_grad):
         box = []
-        x, v, lm, ea, nodes = _PrepareInputsGraph.apply(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, box)
+        x, v, lm, ea, nodes = _PrepareInputsGraph.apply(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, box, batch)
         return x, v, ea, nodes, lm, box[0]
     with torch.no_grad():
-        return _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, bool(tape))
+        return _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, bool(tape), batch)
 
 
 class _PrepareInputsGraph(torch.autograd.Function):
@@ -428,9 +461,10 @@ class _PrepareInputsGraph(torch.autograd.Function):
     explicit list. The graph (not a tensor) leaves through `box`."""
 
     @staticmethod
-    def forward(ctx, loc, vel, n_nodes, charges, t_in, k, r_cut, edges, box):
-        x, v, ea, nodes, lm, g = _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, True)
+    def forward(ctx, loc, vel, n_nodes, charges, t_in, k, r_cut, edges, box, batch):
+        x, v, ea, nodes, lm, g = _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, True, batch)
         box.append(g)
+        ctx.batch = batch
         ctx.shape, ctx.dtypes = tuple(loc.shape), (loc.dtype, vel.dtype)
         ctx.ti = t_in.reshape(-1).to(torch.int32).contiguous() if t_in is not None else None
         ctx.mark_non_differentiable(ea, nodes)
@@ -439,22 +473,31 @@ class _PrepareInputsGraph(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gx, gv, glm, _gea, _gnodes):
-        return _PrepareInputs.backward(ctx, gx, gv, glm, _gea, _gnodes) + (None, None)
+        return _PrepareInputs.backward(ctx, gx, gv, glm, _gea, _gnodes) + (None, None, None)
 
 
-def _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, by_sender):
-    """prepare_inputs_graph off the tape (callers hold torch.no_grad())."""
+def _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, by_sender, batch=None):
+    """prepare_inputs_graph off the tape (callers hold torch.no_grad()). batch: a RaggedBatch or None."""
     from . import graph as _graph
     _graph_source(k, r_cut, edges, "prepare_inputs_graph")
-    if loc.dim() not in (3, 4) or loc.shape != vel.shape or loc.shape[-1] != 3:
-        raise ValueError(f"prepare_inputs_graph: loc, vel must be [B, N, 3] or [F, B, N, 3] alike, got "
-                         f"{tuple(loc.shape)}, {tuple(vel.shape)}")
-    if loc.dim() == 3:
-        loc, vel = loc.unsqueeze(0), vel.unsqueeze(0)
-    F, B, N = loc.shape[0], loc.shape[1], loc.shape[2]
-    if N != n_nodes:
-        raise ValueError(f"prepare_inputs_graph: loc has {N} nodes per graph, n_nodes={n_nodes}")
-    BN = B * N
+    if batch is None:
+        if loc.dim() not in (3, 4) or loc.shape != vel.shape or loc.shape[-1] != 3:
+            raise ValueError(f"prepare_inputs_graph: loc, vel must be [B, N, 3] or [F, B, N, 3] alike, got "
+                             f"{tuple(loc.shape)}, {tuple(vel.shape)}")
+        if loc.dim() == 3:
+            loc, vel = loc.unsqueeze(0), vel.unsqueeze(0)
+        F, B, N = loc.shape[0], loc.shape[1], loc.shape[2]
+        if N != n_nodes:
+            raise ValueError(f"prepare_inputs_graph: loc has {N} nodes per graph, n_nodes={n_nodes}")
+        BN = B * N
+    else:
+        B, BN = batch.n_graphs, batch.n_total
+        if loc.dim() not in (2, 3) or loc.shape != vel.shape or tuple(loc.shape[-2:]) != (BN, 3):
+            raise ValueError(f"prepare_inputs_graph: with sizes, loc, vel must be [{BN}, 3] or [F, {BN}, 3] alike, "
+                             f"got {tuple(loc.shape)}, {tuple(vel.shape)}")
+        if loc.dim() == 2:
+            loc, vel = loc.unsqueeze(0), vel.unsqueeze(0)
+        F = loc.shape[0]
     if charges is not None and charges.numel() != BN:
         raise ValueError(f"prepare_inputs_graph: charges must hold {BN} values, got {charges.numel()}")
     if t_in is not None and t_in.numel() != B:
@@ -475,10 +518,15 @@ def _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, by_
     lm = torch.empty(BN, 3, device=dev)
     L = _lib.lib()
     s = _lib.stream_of(loc)
-    _lib.check(L.nonode_prepare_nodes(B, N, F, _lib.ptr(loc), _lib.ptr(vel), _lib.ptr(ti), _lib.ptr(q), _lib.ptr(x),
-                                      _lib.ptr(v), _lib.ptr(nodes), _lib.ptr(lm), s))
+    io = (_lib.ptr(loc), _lib.ptr(vel), _lib.ptr(ti), _lib.ptr(q), _lib.ptr(x), _lib.ptr(v), _lib.ptr(nodes),
+          _lib.ptr(lm), s)
+    if batch is None:
+        _lib.check(L.nonode_prepare_nodes(B, N, F, *io))
+    else:
+        _lib.check(L.nonode_prepare_nodes_ragged(B, BN, F, _lib.ptr(batch.graph_ptr), *io))
     if edges is None:
-        edges = _graph.neighbor_graph(x, B, N, k, r_cut, by_sender=by_sender)
+        edges = (_graph.neighbor_graph(x, B, N, k, r_cut, by_sender=by_sender) if batch is None else
+                 _graph.neighbor_graph_ragged(x, batch, k, r_cut, by_sender=by_sender))
         rows, cols = edges.rows, edges.col
     n_edges = edges.n_edges if isinstance(edges, _graph.NeighborGraph) else None
     rows, cols = rows.contiguous(), cols.contiguous()
@@ -496,16 +544,76 @@ def _general_model(model, cls, who):
                          "the full-graph drivers take the fully connected list")
 
 
+class _Layout:
+    """How a driver's n_total rows split into graphs: B graphs of N rows (batch None), or the graphs of a
+    graph.RaggedBatch (sizes=; N None). The one thing in which the equal-size and the mixed-size call of a
+    driver differ: its segment loop asks this object for the views and passes it on."""
+
+    def __init__(self, who, loc, n_nodes, batch_size, sizes):
+        if sizes is None:
+            self.batch, self.B, self.N = None, int(batch_size), n_nodes
+            self.n_total = self.B * self.N if n_nodes is not None else None
+            return
+        from .graph import as_batch
+        self.batch = as_batch(sizes, loc.device)
+        self.B, self.N, self.n_total = self.batch.n_graphs, None, self.batch.n_total
+        if batch_size is not None and batch_size != self.B:
+            raise ValueError(f"{who}: batch_size = {batch_size} with {self.B} sizes (leave it None with sizes)")
+        if n_nodes is not None and any(s != n_nodes for s in self.batch.sizes):
+            raise ValueError(f"{who}: n_nodes = {n_nodes} with sizes {self.batch.sizes!r} (leave it None with sizes)")
+
+    def first(self, who, loc, vel):
+        """The shape check of the driver's loc, vel: [B, N, 3] (EGNO, equal sizes) or [n_total, 3]."""
+        want = (self.B, self.N, 3) if self.batch is None else (self.n_total, 3)
+        if tuple(loc.shape) != want or loc.shape != vel.shape:
+            raise ValueError(f"{who}: loc, vel must be [{', '.join(map(str, want))}], got {tuple(loc.shape)}, "
+                             f"{tuple(vel.shape)}")
+
+    def shared_timesteps(self, who, timesteps_out):
+        if self.batch is not None and timesteps_out is not None and timesteps_out.dim() == 2 and \
+                timesteps_out.shape[0] > 1:
+            raise ValueError(f"{who}: a batch of mixed sizes takes shared timesteps only (timesteps_out with one "
+                             f"row, got {timesteps_out.shape[0]}): the embedding maps rows to nodes by equal division")
+
+    def frames(self, t, T=None):
+        """t [(T) n_total, 3] as prepare_inputs_graph takes it: [(T,) B, N, 3] or [(T,) n_total, 3]."""
+        lead = () if T is None else (T,)
+        return t.reshape(*lead, self.B, self.N, 3) if self.batch is None else t.reshape(*lead, self.n_total, 3)
+
+    def prepare(self, loc, vel, charges, t_in=None, **kw):
+        return prepare_inputs_graph(loc, vel, self.N, charges, t_in, sizes=self.batch, **kw)
+
+    def energy(self, dataset, x, v, charges):
+        return conserved_energy(dataset, x, v, charges, self.B, sizes=self.batch)
+
+
+def _segno_layout(who, loc, vel, batch_size, sizes):
+    """The _Layout of a SEGNO driver's loc, vel [n_total, 3] after their shape check: batch_size graphs of
+    n_total / batch_size rows, or the graphs of sizes."""
+    if sizes is not None:
+        lay = _Layout(who, loc, None, batch_size, sizes)
+        lay.first(who, loc, vel)
+        return lay
+    B = int(batch_size)
+    if loc.dim() != 2 or loc.shape[1] != 3 or loc.shape != vel.shape or B < 1 or loc.shape[0] % B:
+        raise ValueError(f"{who}: loc, vel must be [BN, 3] with BN a multiple of batch_size={B}, got "
+                         f"{tuple(loc.shape)}, {tuple(vel.shape)}")
+    return _Layout(who, loc, loc.shape[0] // B, B, None)
+
+
 @torch.no_grad()
 def egno_rollout_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, *, k=None, r_cut=None, edges=None,
-                       timesteps_in=None, timesteps_out=None, energy_dataset=None, return_graphs=False):
+                       timesteps_in=None, timesteps_out=None, energy_dataset=None, return_graphs=False, sizes=None):
     """rollout_fn (main_simulation_simple_no.py:342-384), num_inputs == 1, on a general graph, as a loop of
     model(...) segments like _egno_rollout_segments. loc, vel [B, N, 3]. Per segment: prepare_inputs_graph
     on the current frame (k: the neighbour graph is rebuilt from that frame on the device; edges: the
     topology is fixed and only the features are recomputed), the forward, frame timesteps_in - 1 of each
     sample (None: the last) as the next input, conserved_energy per frame if asked. Nothing in the loop
     reads the device. Returns (loc_preds [traj_len*T, BN, 3], energies, energies_allsteps) as egno_rollout
-    does, and with return_graphs=True also the list of the segments' graphs."""
+    does, and with return_graphs=True also the list of the segments' graphs.
+    sizes (a graph.RaggedBatch or a host sequence; n_nodes and batch_size None): G graphs of mixed sizes in
+    the one loop. loc, vel [n_total, 3], timesteps_in [G], timesteps_out shared (one row); loc_preds
+    [traj_len*T, n_total, 3], energies [.., G, 1]."""
     from .egno import EGNO
     _general_model(model, EGNO, "egno_rollout_graph")
     if model.num_inputs > 1:
@@ -514,11 +622,10 @@ def egno_rollout_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, 
         raise NotImplementedError("egno_rollout_graph does not run with flat=True (general graphs)")
     _graph_source(k, r_cut, edges, "egno_rollout_graph")
     T = model.num_timesteps
-    B, N = batch_size, n_nodes
-    BN = B * N
-    if loc.dim() != 3 or tuple(loc.shape) != (B, N, 3) or loc.shape != vel.shape:
-        raise ValueError(f"egno_rollout_graph: loc, vel must be [{B}, {N}, 3], got {tuple(loc.shape)}, "
-                         f"{tuple(vel.shape)}")
+    lay = _Layout("egno_rollout_graph", loc, n_nodes, batch_size, sizes)
+    lay.first("egno_rollout_graph", loc, vel)
+    lay.shared_timesteps("egno_rollout_graph", timesteps_out)
+    B, BN = lay.B, lay.n_total
     if timesteps_in is not None and timesteps_in.numel() != B:
         raise ValueError(f"egno_rollout_graph: timesteps_in must hold one value per sample ({B}), got "
                          f"{timesteps_in.numel()}")
@@ -531,17 +638,17 @@ def egno_rollout_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, 
     ti = timesteps_in.reshape(-1) if timesteps_in is not None else None   # None: the last frame (t_in = T)
     preds = torch.empty(traj_len * T, BN, 3, device=dev)
     en_all, graphs = [], []
-    x, v, edge_attr, nodes, loc_mean, g = prepare_inputs_graph(loc, vel, N, charges, k=k, r_cut=r_cut, edges=edges)
+    x, v, edge_attr, nodes, loc_mean, g = lay.prepare(loc, vel, charges, k=k, r_cut=r_cut, edges=edges)
     for i in range(traj_len):
         graphs.append(g)
         t_out = timesteps_out[:, i * T:(i + 1) * T] - i * T
         x, v, _ = model(x, nodes, g, edge_attr, v=v, loc_mean=loc_mean, timesteps_out=t_out)
         preds[i * T:(i + 1) * T] = x.reshape(T, BN, 3)
         if energy_dataset is not None:
-            en_all.append(conserved_energy(energy_dataset, x.reshape(T, BN, 3), v.reshape(T, BN, 3), charges, B))
+            en_all.append(lay.energy(energy_dataset, x.reshape(T, BN, 3), v.reshape(T, BN, 3), charges))
         if i + 1 < traj_len:
-            x, v, edge_attr, nodes, loc_mean, g = prepare_inputs_graph(
-                x.reshape(T, B, N, 3), v.reshape(T, B, N, 3), N, charges, ti, k=k, r_cut=r_cut, edges=edges)
+            x, v, edge_attr, nodes, loc_mean, g = lay.prepare(lay.frames(x, T), lay.frames(v, T), charges, ti, k=k,
+                                                              r_cut=r_cut, edges=edges)
     tail = (graphs,) if return_graphs else ()
     if energy_dataset is None:
         return (preds, None, None) + tail
@@ -550,7 +657,7 @@ def egno_rollout_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, 
 
 
 def egno_rollout_train_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, *, k=None, r_cut=None,
-                             edges=None, timesteps_in=None, timesteps_out=None, return_graphs=False):
+                             edges=None, timesteps_in=None, timesteps_out=None, return_graphs=False, sizes=None):
     """The loop of egno_rollout_graph on the autograd tape (unrolled rollout training on a general graph),
     num_inputs == 1, for a model built with graph="trainable". loc, vel [B, N, 3]. Per segment:
     prepare_inputs_graph(tape=True) on the selected frame (k: the neighbour graph, with its CSR by sender, is
@@ -559,7 +666,9 @@ def egno_rollout_train_graph(model, loc, vel, charges, n_nodes, batch_size, traj
     segments' graphs): a loss on it backpropagates through every segment to the parameters and to the
     initial loc and vel. No gradient flows through the choice of neighbours (it is discrete) or through
     nodes / edge_attr (detached, as the reference does at main_simulation_simple_no.py:333,338). No
-    energies. Nothing in the loop or in the backward reads the device."""
+    energies. Nothing in the loop or in the backward reads the device.
+    sizes: G graphs of mixed sizes, as in egno_rollout_graph (loc, vel [n_total, 3], timesteps_in [G], shared
+    timesteps_out; the per-graph mean and its reverse are each graph's own)."""
     from . import graph as _graph
     from .egno import EGNO
     who = "egno_rollout_train_graph"
@@ -573,10 +682,10 @@ def egno_rollout_train_graph(model, loc, vel, charges, n_nodes, batch_size, traj
         raise NotImplementedError(f"{who} does not run with flat=True (general graphs)")
     _graph_source(k, r_cut, edges, who)
     T = model.num_timesteps
-    B, N = batch_size, n_nodes
-    BN = B * N
-    if loc.dim() != 3 or tuple(loc.shape) != (B, N, 3) or loc.shape != vel.shape:
-        raise ValueError(f"{who}: loc, vel must be [{B}, {N}, 3], got {tuple(loc.shape)}, {tuple(vel.shape)}")
+    lay = _Layout(who, loc, n_nodes, batch_size, sizes)
+    lay.first(who, loc, vel)
+    lay.shared_timesteps(who, timesteps_out)
+    B, BN = lay.B, lay.n_total
     if timesteps_in is not None and timesteps_in.numel() != B:
         raise ValueError(f"{who}: timesteps_in must hold one value per sample ({B}), got {timesteps_in.numel()}")
     _lib.require_device(loc, vel, charges, model.embedding.weight)
@@ -590,58 +699,53 @@ def egno_rollout_train_graph(model, loc, vel, charges, n_nodes, batch_size, traj
     preds, graphs = [], []
     x, v, t_in = loc, vel, None
     for i in range(traj_len):
-        x, v, edge_attr, nodes, loc_mean, g = prepare_inputs_graph(x, v, N, charges, t_in, k=k, r_cut=r_cut,
-                                                                   edges=edges, tape=True)
+        x, v, edge_attr, nodes, loc_mean, g = lay.prepare(x, v, charges, t_in, k=k, r_cut=r_cut, edges=edges, tape=True)
         graphs.append(g)
         t_out = timesteps_out[:, i * T:(i + 1) * T] - i * T
         x, v, _ = model(x, nodes, g, edge_attr, v=v, loc_mean=loc_mean, timesteps_out=t_out)
         preds.append(x.reshape(T, BN, 3))
-        x, v, t_in = x.reshape(T, B, N, 3), v.reshape(T, B, N, 3), ti
+        x, v, t_in = lay.frames(x, T), lay.frames(v, T), ti
     preds = torch.cat(preds)
     return (preds, graphs) if return_graphs else preds
 
 
 @torch.no_grad()
 def segno_rollout_graph(model, loc, vel, charges, batch_size, traj_len, num_steps=10, *, k=None, r_cut=None,
-                        edges=None, energy_dataset=None, return_graphs=False):
+                        edges=None, energy_dataset=None, return_graphs=False, sizes=None):
     """rollout_fn (train_nbody.py:200-236), num_prev == 1, on a general graph, as a loop of model(...)
     segments. loc, vel [BN, 3]; his = |v|; num_steps an int or a list of length traj_len. The graph (k:
     rebuilt on the device; edges: fixed) and the edge attributes [q_r q_c, |x_r - x_c|^2] come from each
     segment's start and stay frozen over its substeps, as in nonode_segno_forward_step_graph. Nothing in
     the loop reads the device. Returns (loc_preds [traj_len, BN, 3], energies [traj_len, B, 1] or None), and
-    with return_graphs=True also the list of the segments' graphs."""
+    with return_graphs=True also the list of the segments' graphs.
+    sizes (a graph.RaggedBatch or a host sequence; batch_size None or len(sizes)): G graphs of mixed sizes in
+    the one loop. loc, vel [n_total, 3]; energies [traj_len, G, 1]."""
     from .segno import SEGNO
     _general_model(model, SEGNO, "segno_rollout_graph")
     if model.bug_compat:
         raise ValueError("segno_rollout_graph integrates (bug_compat=True would return the inputs every segment)")
     _graph_source(k, r_cut, edges, "segno_rollout_graph")
-    B = int(batch_size)
-    if loc.dim() != 2 or loc.shape[1] != 3 or loc.shape != vel.shape or B < 1 or loc.shape[0] % B:
-        raise ValueError(f"segno_rollout_graph: loc, vel must be [BN, 3] with BN a multiple of batch_size={B}, got "
-                         f"{tuple(loc.shape)}, {tuple(vel.shape)}")
+    lay = _segno_layout("segno_rollout_graph", loc, vel, batch_size, sizes)
     steps = list(num_steps) if isinstance(num_steps, (list, tuple)) else [int(num_steps)] * traj_len
     if len(steps) != traj_len:
         raise ValueError("num_steps should be a list of length traj_len")
     _lib.require_device(loc, vel, charges, model.embedding.weight)
-    BN = loc.shape[0]
-    N = BN // B
-    preds = torch.empty(traj_len, BN, 3, device=loc.device)
+    preds = torch.empty(traj_len, lay.n_total, 3, device=loc.device)
     en, graphs = [], []
     x, v = loc, vel
     for i, T in enumerate(steps):
-        x, v, edge_attr, nodes, _, g = prepare_inputs_graph(x.reshape(B, N, 3), v.reshape(B, N, 3), N, charges,
-                                                            k=k, r_cut=r_cut, edges=edges)
+        x, v, edge_attr, nodes, _, g = lay.prepare(lay.frames(x), lay.frames(v), charges, k=k, r_cut=r_cut, edges=edges)
         graphs.append(g)
         x, _, v = model(nodes[:, :1], x, g, v, edge_attr, T=int(T))
         preds[i] = x
         if energy_dataset is not None:
-            en.append(conserved_energy(energy_dataset, x, v, charges, B))
+            en.append(lay.energy(energy_dataset, x, v, charges))
     tail = (graphs,) if return_graphs else ()
     return (preds, (torch.stack(en).unsqueeze(-1) if en else None)) + tail
 
 
 def segno_rollout_train_graph(model, loc, vel, charges, batch_size, traj_len, num_steps=10, *, k=None, r_cut=None,
-                              edges=None, return_graphs=False):
+                              edges=None, return_graphs=False, sizes=None):
     """The loop of segno_rollout_graph on the autograd tape (unrolled rollout training on a general graph),
     num_prev == 1, for a model built with graph="any", trainable=True. loc, vel [BN, 3]; num_steps an int or a
     list of length traj_len. Per segment: prepare_inputs_graph(tape=True) on the previous segment's predicted
@@ -651,7 +755,7 @@ def segno_rollout_train_graph(model, loc, vel, charges, batch_size, traj_len, nu
     to the parameters and to the initial loc and vel. No gradient flows through the choice of neighbours (it is
     discrete) or through his = |v| and edge_attr (detached: the reference builds them from data,
     train_nbody.py:121-123,230-233, as egno_rollout_train_graph does). No energies. Nothing in the loop or in
-    the backward reads the device."""
+    the backward reads the device. sizes: G graphs of mixed sizes, as in segno_rollout_graph."""
     from . import graph as _graph
     from .segno import SEGNO
     who = "segno_rollout_train_graph"
@@ -663,22 +767,18 @@ def segno_rollout_train_graph(model, loc, vel, charges, batch_size, traj_len, nu
     if model.bug_compat:
         raise ValueError(f"{who} integrates (bug_compat=True would return the inputs every segment)")
     _graph_source(k, r_cut, edges, who)
-    B = int(batch_size)
-    if loc.dim() != 2 or loc.shape[1] != 3 or loc.shape != vel.shape or B < 1 or loc.shape[0] % B:
-        raise ValueError(f"{who}: loc, vel must be [BN, 3] with BN a multiple of batch_size={B}, got "
-                         f"{tuple(loc.shape)}, {tuple(vel.shape)}")
+    lay = _segno_layout(who, loc, vel, batch_size, sizes)
     steps = list(num_steps) if isinstance(num_steps, (list, tuple)) else [int(num_steps)] * traj_len
     if len(steps) != traj_len:
         raise ValueError("num_steps should be a list of length traj_len")
     _lib.require_device(loc, vel, charges, model.embedding.weight)
-    N = loc.shape[0] // B
     if isinstance(edges, _graph.NeighborGraph):
         edges = edges.with_sender_csr()   # (a graph that came out of a rollout)
     preds, graphs = [], []
     x, v = loc, vel
     for T in steps:
-        x, v, edge_attr, nodes, _, g = prepare_inputs_graph(x.reshape(B, N, 3), v.reshape(B, N, 3), N, charges,
-                                                            k=k, r_cut=r_cut, edges=edges, tape=True)
+        x, v, edge_attr, nodes, _, g = lay.prepare(lay.frames(x), lay.frames(v), charges, k=k, r_cut=r_cut,
+                                                   edges=edges, tape=True)
         graphs.append(g)
         x, _, v = model(nodes[:, :1].detach(), x, g, v, edge_attr.detach(), T=int(T))
         preds.append(x)

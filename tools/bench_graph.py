@@ -1,7 +1,7 @@
 """Timings of the general-graph path (EGNO graph="any", csrc/nonode_graph.hip) on the GPU. One JSON
 line per case on stdout (DESIGN.md section 3.7 quotes them; raw lines under profiles/graph/).
 
-python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|knn_rollout_train|segno_train|all] [--reps 7] [--iters 20] [--arm both|ours]
+python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|ragged_rollout|knn_rollout_train|segno_train|all] [--reps 7] [--iters 20] [--arm both|ours]
 
   price  the C2 graph (B = 512, N = 20, T = 10: 5120 fully connected graphs per layer launch) through
          the fused layer entry (nonode_egnn_layer) and, passed as an edge list, through the general one
@@ -22,6 +22,12 @@ python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|knn_rollout_
          against the loop a user writes without them: knn_graph below (cdist + topk), torch featurisation
          on that list, model(graph="any"), alternated likewise. --arm ours runs the first arm alone (for a
          rocprofv3 --kernel-trace --stats run of its own: the builder's and the featuriser's share).
+  ragged_rollout  graphs of mixed sizes in one batch: eight systems of 250 .. 1750 nodes (8000 in all, the node count
+         of knn_rollout), k = 16, T = 10, 4 layers, traj_len = 4, the damped heads of knn_rollout.
+         harness.egno_rollout_graph(sizes=...) on the batch in one call against the same eight systems rolled out
+         one after another through the equal-size driver with batch_size = 1 (eight times the launches, each at
+         a fraction of the machine), alternated likewise, after one check that the two agree per system. Whole-
+         rollout times (host loop and every launch), not kernel times.
   knn_rollout_train  the knn case trained through an unrolled rollout: traj_len = 2 segments, the graph rebuilt
          from the predicted positions every segment, forward + backward of a loss on every predicted frame.
          harness.egno_rollout_train_graph (the padded NeighborGraph with its device-built CSR by sender on the
@@ -323,6 +329,64 @@ def case_knn_rollout(args):
     return res
 
 
+def case_ragged_rollout(args):
+    SIZES, T, K, SEG, DAMP = (250, 500, 750, 1000, 1000, 1250, 1500, 1750), 10, 16, 4, 0.01
+    G, n = len(SIZES), sum(SIZES)
+    gen = torch.Generator().manual_seed(2)
+    parts = []
+    for s in SIZES:   # each system at the knn case's density for its own size
+        sigma = (s / 5.0) ** (1.0 / 3.0)
+        lo, ve = torch.randn(s, 3, generator=gen) * sigma, torch.randn(s, 3, generator=gen)
+        parts.append((lo, ve / ve.norm(dim=-1, keepdim=True) * 0.5, (torch.randint(0, 2, (s, 1), generator=gen) * 2 - 1).float()))
+    loc, vel, q = (torch.cat([p[i] for p in parts]).to(DEV) for i in range(3))
+    off = np.concatenate([[0], np.cumsum(SIZES)])
+    t_out = torch.arange(1, T * SEG + 1, device=DEV).unsqueeze(0)   # shared timesteps: one row
+    m = model(T, graph="any")
+    with torch.no_grad():   # the damped heads of the knn_rollout case: the positions stay bounded over the segments
+        for layer in m.layers:
+            for head in (layer.coord_net, layer.node_v_net):
+                head.mlp[2].weight.mul_(DAMP)
+                head.mlp[2].bias.mul_(DAMP)
+    batch = graph.RaggedBatch(SIZES, DEV)
+    one = [(loc[off[g]:off[g + 1]].reshape(1, SIZES[g], 3).contiguous(), vel[off[g]:off[g + 1]].reshape(1, SIZES[g], 3).contiguous(),
+            q[off[g]:off[g + 1]].contiguous()) for g in range(G)]
+
+    def ragged():
+        return harness.egno_rollout_graph(m, loc, vel, q, None, None, SEG, k=K, timesteps_out=t_out, sizes=batch)[0]
+
+    def one_by_one():
+        return [harness.egno_rollout_graph(m, lo, ve, qq, SIZES[g], 1, SEG, k=K, timesteps_out=t_out)[0]
+                for g, (lo, ve, qq) in enumerate(one)]
+
+    # before timing: the batch's positions against each system rolled out alone, segment 1 at 1e-5, later segments
+    # at 1e-5 too here (the two arms run the same kernels on the same lists unless a tie breaks differently, which
+    # the builder's total order excludes); the figures go into the line
+    a, b = ragged(), one_by_one()
+    torch.cuda.synchronize()
+    parity = []
+    for i in range(SEG):
+        err = max(float((a[i * T:(i + 1) * T, off[g]:off[g + 1]] - b[g][i * T:(i + 1) * T]).abs().max() /
+                        b[g][i * T:(i + 1) * T].abs().max()) for g in range(G))
+        parity.append(err)
+    if not all(e < 1e-5 for e in parity):
+        raise SystemExit(f"ragged_rollout: the batch and the systems rolled out alone differ: {parity}")
+    iters = max(args.iters // 4, 3)
+    t = alternate({"ragged": ragged, "one_by_one": one_by_one}, args.reps, iters)
+    ra, rb = stats(t["ragged"]), stats(t["one_by_one"])
+    return {"case": "ragged_rollout", "what": "whole-rollout time (host loop and every launch), not a kernel time",
+            "shape": {"sizes": list(SIZES), "n_total": n, "k": K, "T": T, "layers": 4, "traj_len": SEG,
+                      "capacity": batch.capacity(K)},
+            "iters_per_rep": iters,
+            "model": f"untrained, last layers of coord_net and node_v_net scaled by {DAMP} (both arms)",
+            "segment_maxnorm_rel_vs_one_by_one": parity,
+            "ragged_one_call": ra, "ragged_per_rep_ms": t["ragged"],
+            "one_by_one_batch_size_1": rb, "one_by_one_per_rep_ms": t["one_by_one"],
+            "speedup_over_one_by_one": rb["median_ms"] / ra["median_ms"],
+            "not_slower": ra["median_ms"] <= rb["median_ms"],
+            "not_slower_on_any_alternation": all(x <= y for x, y in zip(t["ragged"], t["one_by_one"])),
+            "last_frame_absmax": float(a[-1].abs().max())}
+
+
 def case_knn_rollout_train(args):
     B, N, T, K, SEG, DAMP = 8, 1000, 10, 16, 2, 0.01
     loc, vel, q = synthetic(B, N, 2)
@@ -439,7 +503,8 @@ def case_segno_train(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", default="all", choices=["price", "knn", "knn_train", "knn_rollout", "knn_rollout_train", "segno_train", "all"])
+    ap.add_argument("--case", default="all", choices=["price", "knn", "knn_train", "knn_rollout", "ragged_rollout", "knn_rollout_train", "segno_train",
+                                                    "all"])
     ap.add_argument("--arm", default="both", choices=["both", "ours"], help="knn_train, knn_rollout, knn_rollout_train, segno_train: the HIP arm alone")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
@@ -447,7 +512,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_graph.py measures on the GPU: no ROCm device found")
     for name, fn in (("price", case_price), ("knn", case_knn), ("knn_train", case_knn_train),
-                     ("knn_rollout", case_knn_rollout), ("knn_rollout_train", case_knn_rollout_train),
+                     ("knn_rollout", case_knn_rollout), ("ragged_rollout", case_ragged_rollout),
+                     ("knn_rollout_train", case_knn_rollout_train),
                      ("segno_train", case_segno_train)):
         if args.case in (name, "all"):
             res = fn(args)
