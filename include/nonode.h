@@ -747,6 +747,45 @@ int nonode_neighbor_graph_ragged(int G, int n_total, int n_max, int k, long long
                                  int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The same graph under a FINITE cut-off from a cell list instead of the search over all N_g nodes of a graph:
+ * for every input, row_ptr, col, rows, eid and the (-1, -1, p) tail are bitwise what
+ * nonode_neighbor_graph_ragged (nonode_neighbor_graph) writes; only the work differs, O(cells a cut-off box
+ * touches) per receiver instead of O(N_g). Arguments as nonode_neighbor_graph_ragged; graph_ptr and graph_of
+ * both NULL: G graphs of n_max rows each (n_total = G*n_max). Each graph's finite nodes are binned into a
+ * uniform grid of g cells per axis, g the largest integer with 4 g^3 <= N_g, cell width max(rr, extent / g)
+ * per axis, rr a search radius just above sqrt(r2_max) with rr*rr > r2_max in f32; the nodes are sorted by
+ * cell and one wave per receiver walks the cells cell(x_i - rr) .. cell(x_i + rr) of every axis, feeding the
+ * same distances and keys into the same keep-the-k-smallest code. One binning function, built from
+ * individually rounded (hence monotone) f32 operations, bins the nodes and bounds the box, which is why no
+ * candidate is missed whatever the rounding (csrc/nonode_cells.h). A node with a non-finite coordinate gets
+ * degree 0 and is in no row, as the contract above implies under a finite r2_max. A stretched extent (one
+ * outlier, a diverged rollout) leaves most nodes in few cells: the same graph, found more slowly.
+ * Integer atomics count the cells and claim the sorted slots, so the order inside a cell varies from run to run;
+ * the rows do not (the top k of a set under a total order). No launch, allocation or grid sized from device data.
+ * Refused with NONODE_EINVAL: what nonode_neighbor_graph_ragged refuses, r2_max not finite, one of graph_ptr /
+ * graph_of NULL and the other not, equal sizes with n_total != G*n_max, a workspace not 16-byte aligned.
+ * Every store is guarded against a descriptor that disagrees with n_total or cap. Asynchronous.
+ * Workspace: nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k) =
+ * (n_total*(8 + min(k, n_max - 1)) + 8 G + 1) ints (the sorted positions, the rows at one fixed pitch, the cell
+ * table of n_total + G entries and its scan); 0 for refused arguments.
+ */
+size_t nonode_neighbor_graph_cells_workspace_bytes(int G, int n_total, int n_max, int k);
+int nonode_neighbor_graph_cells(int G, int n_total, int n_max, int k, long long cap, float r2_max,
+                                const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
+                                int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Diagnostic, HOST arrays and no device: the grid, the binning and the search boxes of
+ * nonode_neighbor_graph_cells, computed by the functions its kernels run. graph_ptr [G + 1] (NULL: G graphs
+ * of n_max rows), x [n_total][3]. Outputs (each may be NULL): rr_out [1] the search radius; grid [G] the cells
+ * per axis; box [G][9] = lower corner, upper corner, 1 / cell width per axis; cell [n_total][3] every node's
+ * cell per axis (-1: a non-finite node has none); range [n_total][6] = the lowest and the highest cell per
+ * axis that the node searches as a receiver (-1 for a non-finite node). Returns NONODE_OK or NONODE_EINVAL.
+ */
+int nonode_debug_neighbor_cells(int G, int n_total, int n_max, float r2_max, const int* graph_ptr, const float* x,
+                                float* rr_out, int* grid, float* box, int* cell, int* range);
+
+/*
  * The same graph as a CSR by sender, which the reverse pass of the graph layer
  * (nonode_egnn_layer_graph_bwd) walks: what training on a graph rebuilt every step needs, made on the
  * device from the padded list and its device-side count (nonode_graph_build cannot take a list with a

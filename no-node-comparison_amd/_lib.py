@@ -47,6 +47,7 @@ SYMBOLS = (
     "nonode_segno_graph_train_state_bytes", "nonode_segno_forward_train_graph", "nonode_segno_layer_graph_bwd",
     "nonode_neighbor_graph_ragged_workspace_bytes", "nonode_neighbor_graph_ragged", "nonode_prepare_nodes_ragged",
     "nonode_prepare_inputs_bwd_ragged", "nonode_energy_ragged",
+    "nonode_neighbor_graph_cells_workspace_bytes", "nonode_neighbor_graph_cells", "nonode_debug_neighbor_cells",
 )
 
 VARIANT_EGNO = 0
@@ -273,6 +274,10 @@ def lib():
     L.nonode_neighbor_graph_ragged_workspace_bytes.argtypes = [_i] * 3
     L.nonode_neighbor_graph_ragged_workspace_bytes.restype = _sz
     L.nonode_neighbor_graph_ragged.argtypes = [_i] * 4 + [_ll, _f] + [_vp] * 8 + [_sz, _vp]
+    L.nonode_neighbor_graph_cells_workspace_bytes.argtypes = [_i] * 4
+    L.nonode_neighbor_graph_cells_workspace_bytes.restype = _sz
+    L.nonode_neighbor_graph_cells.argtypes = L.nonode_neighbor_graph_ragged.argtypes
+    L.nonode_debug_neighbor_cells.argtypes = [_i, _i, _i, _f] + [_vp] * 7
     L.nonode_prepare_nodes_ragged.argtypes = [_i] * 3 + [_vp] * 10
     L.nonode_prepare_inputs_bwd_ragged.argtypes = [_i] * 3 + [_vp] * 8
     L.nonode_energy_ragged.argtypes = [_i] * 4 + [_vp] * 6

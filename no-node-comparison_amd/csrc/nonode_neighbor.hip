@@ -14,6 +14,10 @@
 //   neighbor_select_kernel  one wave per receiver: the min(k, candidates) smallest candidates under
 //                           the total order (d2, j), kept sorted across the 64 lanes; the row written
 //                           by ascending sender at a fixed pitch, and its degree
+//   cell_bbox / _count / _fill_kernel, neighbor_select_cells_kernel  the same rows under a finite cut-off from
+//                           a cell list (nonode_neighbor_graph_cells): each graph's nodes binned into a
+//                           uniform grid and sorted by cell, one wave per receiver over the cells its cut-off
+//                           box touches, the candidates through the same keep-the-k-smallest body
 //   (scan)                  row_ptr = exclusive prefix sum of the degrees (nonode_graph.hip's
 //                           one-workgroup scan)
 //   neighbor_compact_kernel fixed-pitch rows -> CSR (col, rows, eid), and the -1 tail
@@ -30,6 +34,8 @@
 #include "nonode_common.h"
 
 #pragma clang fp contract(off)
+
+#include "nonode_cells.h"
 
 namespace {
 
@@ -70,17 +76,53 @@ __device__ __forceinline__ float dist2(float a0, float a1, float a2, float b0, f
   return ((d0 * d0) + (d1 * d1)) + (d2 * d2);
 }
 
-// One wave per receiver r = g0 + i of a graph of N rows from g0 on. Lane l of `best` holds the l-th
-// smallest key seen so far (ascending). Of a chunk of 64 candidates only the keys below the kk-th best
-// matter, kk = min(k, N - 1) (that bound only falls, so a key at or above it never reaches the final kk):
-// none, the chunk is skipped; a few (INSERT_MAX), each is inserted at its rank (one ballot, one lane
-// shift); more, the chunk is sorted and merged in. tmp [n_total][pitch]: the row's senders (global index)
-// ascending; deg [n_total].
+// The keep-the-k-smallest body both searches share. Lane l of `best` holds the l-th smallest key seen so far
+// (ascending). Of a chunk of 64 candidate keys (KEY_NONE: none in that lane) only the keys below the kk-th
+// best matter (that bound only falls, so a key at or above it never reaches the final kk): none, the chunk is
+// skipped; a few (INSERT_MAX), each is inserted at its rank (one ballot, one lane shift); more, the chunk is
+// sorted and merged in. The keys of a row are distinct, so what `best` ends as is the kk smallest of the set
+// of keys fed in, whatever the order and the chunking they came in.
+constexpr int INSERT_MAX = 8;
+__device__ __forceinline__ void topk_chunk(u64& best, u64 key, int kk, int lane) {
+  const u64 kth = shfl64(best, kk - 1);
+  u64 below = __ballot(key < kth);
+  if (!below) return;
+  if (__popcll(below) <= INSERT_MAX) {
+    while (below) {   // (wave-uniform)
+      const u64 nk = shfl64(key, __ffsll((long long)below) - 1);
+      below &= below - 1;
+      const int pos = __popcll(__ballot(best < nk));
+      const u64 up = shfl_up64(best);
+      best = lane < pos ? best : (lane == pos ? nk : up);
+    }
+    return;
+  }
+  key = bitonic_sort(key, lane);
+  // best ascending, the chunk descending: the lane-wise minimum holds the 64 smallest of the 128
+  // as a bitonic sequence, which one merge pass sorts
+  const u64 rev = shfl64(key, 63 - lane);
+  best = bitonic_stages(best < rev ? best : rev, lane, 64, 32);
+}
+// the row of receiver r from its kk best keys: the kept senders by ascending index at tmp [n_total][pitch]
+// (global index), and the degree
+__device__ __forceinline__ void topk_write(u64 best, int kk, int lane, int r, int g0, int pitch,
+                                           int* __restrict__ tmp, int* __restrict__ deg) {
+  const bool kept = lane < kk && best != KEY_NONE;
+  const int d = __popcll(__ballot(kept));
+  // the kept senders by ascending index (the sentinel sorts last)
+  u64 byj = kept ? (u64)(unsigned)best : KEY_NONE;
+  byj = bitonic_sort(byj, lane);
+  if (lane < d) tmp[(size_t)r * pitch + lane] = g0 + (int)(unsigned)byj;
+  if (lane == 0) deg[r] = d;
+}
+
+// One wave per receiver r = g0 + i of a graph of N rows from g0 on, striding over all N nodes of its graph
+// (the brute-force search: any r2_max, +inf included). kk = min(k, N - 1); the chunks go through topk_chunk.
+// tmp [n_total][pitch]: the row's senders (global index) ascending; deg [n_total].
 // The receiver's graph: graph_of null, equal sizes (g0 = (r / n_each) n_each, N = n_each); otherwise graph
 // g = graph_of[r] of n_graphs, rows graph_ptr[g] .. graph_ptr[g + 1] (graph_rows holds them to
 // [0, n_total], and kk to the pitch, so nothing below leaves x, tmp or deg whatever the descriptor says).
 // g0, N and kk are the same in every lane and kept in scalar registers.
-constexpr int INSERT_MAX = 8;
 __global__ __launch_bounds__(256) void neighbor_select_kernel(int n_total, int n_each, int k, int pitch, float r2_max,
                                                               int n_graphs, const int* __restrict__ graph_ptr,
                                                               const int* __restrict__ graph_of,
@@ -108,32 +150,156 @@ __global__ __launch_bounds__(256) void neighbor_select_kernel(int n_total, int n
       // d2 >= +0 here (a NaN fails the compare), so its bits order as an unsigned integer
       if (d2 <= r2_max) key = ((u64)__float_as_uint(d2) << 32) | (unsigned)j;
     }
-    const u64 kth = shfl64(best, kk - 1);
-    u64 below = __ballot(key < kth);
-    if (!below) continue;
-    if (__popcll(below) <= INSERT_MAX) {
-      while (below) {   // (wave-uniform)
-        const u64 nk = shfl64(key, __ffsll((long long)below) - 1);
-        below &= below - 1;
-        const int pos = __popcll(__ballot(best < nk));
-        const u64 up = shfl_up64(best);
-        best = lane < pos ? best : (lane == pos ? nk : up);
-      }
-      continue;
-    }
-    key = bitonic_sort(key, lane);
-    // best ascending, the chunk descending: the lane-wise minimum holds the 64 smallest of the 128
-    // as a bitonic sequence, which one merge pass sorts
-    const u64 rev = shfl64(key, 63 - lane);
-    best = bitonic_stages(best < rev ? best : rev, lane, 64, 32);
+    topk_chunk(best, key, kk, lane);
   }
-  const bool kept = lane < kk && best != KEY_NONE;
-  const int d = __popcll(__ballot(kept));
-  // the kept senders by ascending index (the sentinel sorts last)
-  u64 byj = kept ? (u64)(unsigned)best : KEY_NONE;
-  byj = bitonic_sort(byj, lane);
-  if (lane < d) tmp[(size_t)r * pitch + lane] = g0 + (int)(unsigned)byj;
-  if (lane == 0) deg[r] = d;
+  topk_write(best, kk, lane, r, g0, pitch, tmp, deg);
+}
+
+// ---- the cell-list search (a finite r2_max): the same rows from the cells a receiver's cut-off box touches ----
+// nonode_cells.h has the grid rule, the binning function, the search box and why they miss no candidate.
+// Graph gi of a batch (rows g0 .. g0 + N) owns the N + 1 entries from g0 + gi on of one table of
+// n_total + n_graphs entries: its g^3 <= N / CELL_FILL cells, z fastest, then the bucket of its non-finite
+// nodes. Counts and slot claims are integer atomics, so the order of the nodes inside a cell differs from run
+// to run; that cannot show in the result, as a row is the top k of a SET of keys under a total order
+// (topk_chunk), then sorted by sender. Every index below is held inside its array whatever the descriptor says.
+struct NodeGraph {
+  int gi, g0, n;
+};
+__device__ __forceinline__ NodeGraph node_graph(int r, int n_total, int n_each, int n_graphs,
+                                                const int* __restrict__ graph_ptr, const int* __restrict__ graph_of) {
+  if (!graph_of) return NodeGraph{r / n_each, (r / n_each) * n_each, n_each};
+  const int gi = imin(imax(graph_of[r], 0), n_graphs - 1);
+  const GraphRows gr = graph_rows(graph_ptr, gi, 0, n_total);
+  return NodeGraph{gi, gr.r0, gr.n};
+}
+
+// bb [n_graphs][6], zero before: every graph's bounding box over its finite nodes as integer-ordered maxima
+// (cell_grid reads it back). A wave whose 64 nodes belong to one graph reduces first and sends six atomics.
+__global__ __launch_bounds__(256) void cell_bbox_kernel(int n_total, int n_each, int n_graphs,
+                                                        const int* __restrict__ graph_ptr,
+                                                        const int* __restrict__ graph_of, const float* __restrict__ x,
+                                                        unsigned* bb) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r - (int)(threadIdx.x & 63) >= n_total) return;   // (wave-uniform: lane 0 holds a node below)
+  unsigned m[6] = {0u, 0u, 0u, 0u, 0u, 0u};   // 0: below every finite key
+  int gi = -1;
+  if (r < n_total) {
+    gi = node_graph(r, n_total, n_each, n_graphs, graph_ptr, graph_of).gi;
+    const float x0 = x[(size_t)r * 3 + 0], x1 = x[(size_t)r * 3 + 1], x2 = x[(size_t)r * 3 + 2];
+    if (cell_finite(x0, x1, x2)) {
+      m[3] = cell_key(x0); m[4] = cell_key(x1); m[5] = cell_key(x2);
+      m[0] = ~m[3]; m[1] = ~m[4]; m[2] = ~m[5];
+    }
+  }
+  const int gf = __builtin_amdgcn_readfirstlane(gi);
+  if (__all(gi == gf || gi < 0)) {
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const unsigned t = (unsigned)__shfl_xor((int)m[a], o);
+        m[a] = m[a] > t ? m[a] : t;
+      }
+    }
+    if ((threadIdx.x & 63) != 0) return;
+  }
+  if (gi < 0) return;
+#pragma unroll
+  for (int a = 0; a < 6; ++a)
+    if (m[a]) atomicMax(bb + (size_t)gi * 6 + a, m[a]);
+}
+
+// bucket[r] = the table entry of node r (its cell, or its graph's trailing bucket), counted in cnt
+__global__ __launch_bounds__(256) void cell_count_kernel(int n_total, int n_each, int n_graphs, float rr,
+                                                         const int* __restrict__ graph_ptr,
+                                                         const int* __restrict__ graph_of, const float* __restrict__ x,
+                                                         const unsigned* __restrict__ bb, int* cnt,
+                                                         int* __restrict__ bucket) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_total) return;
+  const NodeGraph ng = node_graph(r, n_total, n_each, n_graphs, graph_ptr, graph_of);
+  const CellGrid cg = cell_grid(bb + (size_t)ng.gi * 6, ng.n, rr);
+  const float x0 = x[(size_t)r * 3 + 0], x1 = x[(size_t)r * 3 + 1], x2 = x[(size_t)r * 3 + 2];
+  int c = cg.g * cg.g * cg.g;
+  if (cell_finite(x0, x1, x2))
+    c = (cell_of(x0, cg.lo[0], cg.inv_w[0], cg.g) * cg.g + cell_of(x1, cg.lo[1], cg.inv_w[1], cg.g)) * cg.g +
+        cell_of(x2, cg.lo[2], cg.inv_w[2], cg.g);
+  const int idx = imin(ng.g0 + ng.gi + c, n_total + n_graphs - 1);
+  bucket[r] = idx;
+  atomicAdd(cnt + idx, 1);
+}
+// every node takes the next free slot of its bucket (cursor: the scan of the counts): sorted [n_total] =
+// (x, y, z, the node's row index as bits), every node exactly once
+__global__ __launch_bounds__(256) void cell_fill_kernel(int n_total, const float* __restrict__ x,
+                                                        const int* __restrict__ bucket, int* cursor,
+                                                        f4* __restrict__ sorted) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_total) return;
+  const int slot = atomicAdd(cursor + bucket[r], 1);
+  if (slot >= 0 && slot < n_total)
+    sorted[slot] = f4{x[(size_t)r * 3 + 0], x[(size_t)r * 3 + 1], x[(size_t)r * 3 + 2], __int_as_float(r)};
+}
+
+// One wave per receiver, taken in sorted order (neighbouring waves walk the same cells). With z the fastest
+// cell index, the cells (cx, cy, z_lo .. z_hi) of the receiver's box are one contiguous run of the sorted order:
+// cell_start[first cell] .. cell_start[last cell + 1]. A run holds about a third of a wave at cut-off-wide cells,
+// so the 64 lanes take several runs at once: groups of 16 lanes (32 with two or three runs, all 64 with one)
+// each stride over one run, and every round's 64 keys are one chunk of topk_chunk. Same dist2, same key
+// (d2, j) with j the node's index inside its graph, as in neighbor_select_kernel.
+// (NONODE_CELLS_PACK=0 builds give every run all 64 lanes, one run per round: the A/B of DESIGN.md section 3.7.1.)
+#ifndef NONODE_CELLS_PACK
+#define NONODE_CELLS_PACK 1
+#endif
+__global__ __launch_bounds__(256) void neighbor_select_cells_kernel(
+    int n_total, int n_each, int k, int pitch, float r2_max, float rr, int n_graphs, const int* __restrict__ graph_ptr,
+    const int* __restrict__ graph_of, const f4* __restrict__ sorted, const int* __restrict__ cell_start,
+    const unsigned* __restrict__ bb, int* __restrict__ tmp, int* __restrict__ deg) {
+  const int lane = threadIdx.x & 63;
+  const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= n_total) return;   // (wave-uniform)
+  const f4 me = sorted[s];
+  const int r = __builtin_amdgcn_readfirstlane(__float_as_int(me[3]));
+  if (r < 0 || r >= n_total) return;   // (the fill wrote every slot: never)
+  const NodeGraph ng = node_graph(r, n_total, n_each, n_graphs, graph_ptr, graph_of);
+  const int g0 = __builtin_amdgcn_readfirstlane(ng.g0), N = __builtin_amdgcn_readfirstlane(ng.n);
+  const int gi = __builtin_amdgcn_readfirstlane(ng.gi);
+  const int kk = imin(imin(k, N - 1), pitch), i = r - g0;
+  const float xi0 = me[0], xi1 = me[1], xi2 = me[2];
+  if (kk <= 0 || !cell_finite(xi0, xi1, xi2)) {   // a graph of one node, a non-finite receiver: no pair
+    if (lane == 0) deg[r] = 0;
+    return;
+  }
+  const CellGrid cg = cell_grid(bb + (size_t)gi * 6, N, rr);
+  const CellBox bx = cell_box(cg, xi0, xi1, xi2, rr);
+  const int g = cg.g, tab = g0 + gi, last = n_total + n_graphs - 1;
+  const int ny = __builtin_amdgcn_readfirstlane(bx.hi[1] - bx.lo[1] + 1);
+  const int nruns = __builtin_amdgcn_readfirstlane((bx.hi[0] - bx.lo[0] + 1) * ny);
+  const int sh = !NONODE_CELLS_PACK ? 6 : (nruns >= 4 ? 4 : (nruns >= 2 ? 5 : 6));   // log2 of the lanes per run
+  const int grp = lane >> sh, sub = lane & ((1 << sh) - 1);
+  u64 best = KEY_NONE;
+  for (int u0 = 0; u0 < nruns; u0 += 64 >> sh) {
+    const int u = u0 + grp;
+    int p = 0, e = 0;
+    if (u < nruns) {
+      const int c = ((bx.lo[0] + u / ny) * g + bx.lo[1] + u % ny) * g;
+      p = cell_start[imin(tab + c + bx.lo[2], last)] + sub;
+      e = cell_start[imin(tab + c + bx.hi[2], last) + 1];
+    }
+    e = imin(e, n_total);
+    while (__any(p < e)) {
+      u64 key = KEY_NONE;
+      if (p >= 0 && p < e) {
+        const f4 o = sorted[p];
+        const int j = __float_as_int(o[3]) - g0;
+        const float d2 = dist2(xi0, xi1, xi2, o[0], o[1], o[2]);
+        // d2 >= +0 here (a NaN fails the compare), so its bits order as an unsigned integer
+        if (j != i && d2 <= r2_max) key = ((u64)__float_as_uint(d2) << 32) | (unsigned)j;
+      }
+      topk_chunk(best, key, kk, lane);
+      p += 1 << sh;
+    }
+  }
+  topk_write(best, kk, lane, r, g0, pitch, tmp, deg);
 }
 
 // thread t = r pitch + l of the n_total pitch fixed-pitch slots: entry l of row r moves to row_ptr[r] + l;
@@ -311,6 +477,54 @@ int launch_neighbor_graph(const char* who, int n_total, int n_max, int k, long l
   return check_launch("neighbor_compact_kernel");
 }
 
+// The cell-list builder's workspace, in ints: sorted (4 n_total, first: 16-byte rows), deg, tmp (as above),
+// bucket (n_total), then bb (6 G) and cnt (n_total + G) side by side (one memset), cell_start (n_total + G + 1).
+size_t cells_workspace_ints(int G, int n_total, int pitch) {
+  return (size_t)n_total * (8 + (size_t)pitch) + 8 * (size_t)G + 1;
+}
+
+// The cell-list builder's launches (finite r2_max): memset, bounding boxes, cell counts, scan, fill, the
+// search, then the brute-force builder's own scan and compaction. Every grid is a function of n_total and the
+// pitch; nothing is read back.
+int launch_neighbor_graph_cells(int n_total, int n_max, int k, long long cap, float r2_max, int n_graphs,
+                                const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
+                                int* eid, int* rows, void* workspace, hipStream_t s) {
+  const char* who = "neighbor_graph_cells";
+  const int pitch = k < n_max - 1 ? k : n_max - 1;
+  if (pitch == 0) {   // graphs of one node: no pair at all
+    if (hipMemsetAsync(row_ptr, 0, ((size_t)n_total + 1) * sizeof(int), s) != hipSuccess)
+      return fail(NONODE_ELAUNCH, "%s: memset", who);
+    return NONODE_OK;
+  }
+  f4* sorted = (f4*)workspace;
+  int* deg = (int*)workspace + 4 * (size_t)n_total;
+  int* tmp = deg + n_total;
+  int* bucket = tmp + (size_t)n_total * pitch;
+  unsigned* bb = (unsigned*)(bucket + n_total);
+  int* cnt = (int*)(bb + 6 * (size_t)n_graphs);
+  int* cell_start = cnt + n_total + n_graphs;
+  const float rr = cell_rr(r2_max);
+  if (hipMemsetAsync(bb, 0, (6 * (size_t)n_graphs + (size_t)n_total + n_graphs) * sizeof(int), s) != hipSuccess)
+    return fail(NONODE_ELAUNCH, "%s: memset", who);
+  const dim3 per_node((n_total + 255) / 256), per_wave((n_total + 3) / 4);
+  hipLaunchKernelGGL(cell_bbox_kernel, per_node, dim3(256), 0, s, n_total, n_max, n_graphs, graph_ptr, graph_of, x, bb);
+  if (int rc = check_launch("cell_bbox_kernel")) return rc;
+  hipLaunchKernelGGL(cell_count_kernel, per_node, dim3(256), 0, s, n_total, n_max, n_graphs, rr, graph_ptr, graph_of,
+                     x, bb, cnt, bucket);
+  if (int rc = check_launch("cell_count_kernel")) return rc;
+  if (int rc = nonode_tu::graph_scan(n_total + n_graphs, cnt, cell_start, s)) return rc;
+  hipLaunchKernelGGL(cell_fill_kernel, per_node, dim3(256), 0, s, n_total, x, bucket, cnt, sorted);
+  if (int rc = check_launch("cell_fill_kernel")) return rc;
+  hipLaunchKernelGGL(neighbor_select_cells_kernel, per_wave, dim3(256), 0, s, n_total, n_max, k, pitch, r2_max, rr,
+                     n_graphs, graph_ptr, graph_of, sorted, cell_start, bb, tmp, deg);
+  if (int rc = check_launch("neighbor_select_cells_kernel")) return rc;
+  if (int rc = nonode_tu::graph_scan(n_total, deg, row_ptr, s)) return rc;
+  const long long slots = (long long)n_total * pitch;
+  hipLaunchKernelGGL(neighbor_compact_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, cap, n_total,
+                     pitch, row_ptr, tmp, col, eid, rows);
+  return check_launch("neighbor_compact_kernel");
+}
+
 int launch_node_features(int n_graphs, int n_total, int n_each, int F, const int* graph_ptr, const float* loc,
                          const float* vel, const int* t_in, const float* charges, float* x_out, float* v_out,
                          float* nodes, float* loc_mean, hipStream_t s) {
@@ -366,6 +580,85 @@ int nonode_neighbor_graph_ragged(int G, int n_total, int n_max, int k, long long
                 nonode_neighbor_graph_ragged_workspace_bytes(n_total, n_max, k));
   return launch_neighbor_graph("neighbor_graph_ragged", n_total, n_max, k, cap, r2_max, G, graph_ptr, graph_of, x,
                                row_ptr, col, eid, rows, workspace, (hipStream_t)stream);
+}
+
+size_t nonode_neighbor_graph_cells_workspace_bytes(int G, int n_total, int n_max, int k) {
+  if (G < 1 || n_total < G || n_total >= (1 << 30) || n_max <= 0 || n_max > n_total || k < 1 || k > 64) return 0;
+  return cells_workspace_ints(G, n_total, k < n_max - 1 ? k : n_max - 1) * sizeof(int);
+}
+
+int nonode_neighbor_graph_cells(int G, int n_total, int n_max, int k, long long cap, float r2_max,
+                                const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
+                                int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream) {
+  if (G < 1 || n_total < G || n_total >= (1 << 30) || n_max < 1 || n_max > n_total || k < 1 || k > 64 ||
+      !(r2_max > 0.f) || !cell_finite(r2_max) || cap < 0 || cap >= (1ll << 31) ||
+      cap > (long long)n_total * (k < n_max - 1 ? k : n_max - 1))
+    return fail(NONODE_EINVAL, "neighbor_graph_cells: G=%d n_total=%d n_max=%d k=%d cap=%lld r2_max=%g (k in [1, 64], "
+                "r2_max > 0 and finite, cap <= n_total min(k, n_max - 1))", G, n_total, n_max, k, cap, (double)r2_max);
+  if ((graph_ptr == nullptr) != (graph_of == nullptr))
+    return fail(NONODE_EINVAL, "neighbor_graph_cells: graph_ptr and graph_of go together (both null: equal sizes)");
+  if (!graph_of && (long long)G * n_max != n_total)
+    return fail(NONODE_EINVAL, "neighbor_graph_cells: equal sizes need n_total = G n_max, got G=%d n_max=%d n_total=%d",
+                G, n_max, n_total);
+  if (!x || !row_ptr || !workspace || (cap > 0 && (!col || !eid || !rows)))
+    return fail(NONODE_EINVAL, "neighbor_graph_cells: null pointer");
+  if (((size_t)workspace & 15) != 0) return fail(NONODE_EINVAL, "neighbor_graph_cells: workspace not 16-byte aligned");
+  if (workspace_bytes < nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k))
+    return fail(NONODE_EINVAL, "neighbor_graph_cells: workspace %zu < %zu", workspace_bytes,
+                nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k));
+  return launch_neighbor_graph_cells(n_total, n_max, k, cap, r2_max, G, graph_ptr, graph_of, x, row_ptr, col, eid, rows,
+                                     workspace, (hipStream_t)stream);
+}
+
+// Diagnostic (host arrays, no GPU): the grid, the binning and the search boxes of the cell-list search, from
+// the very functions its kernels run (nonode_cells.h).
+int nonode_debug_neighbor_cells(int G, int n_total, int n_max, float r2_max, const int* graph_ptr, const float* x,
+                                float* rr_out, int* grid, float* box, int* cell, int* range) {
+  if (G < 1 || n_total < G || n_max < 1 || n_max > n_total || !(r2_max > 0.f) || !cell_finite(r2_max) || !x ||
+      (!graph_ptr && (long long)G * n_max != n_total))
+    return fail(NONODE_EINVAL, "debug_neighbor_cells: G=%d n_total=%d n_max=%d r2_max=%g", G, n_total, n_max,
+                (double)r2_max);
+  const float rr = cell_rr(r2_max);
+  if (rr_out) *rr_out = rr;
+  for (int gi = 0; gi < G; ++gi) {
+    int g0 = gi * n_max, n = n_max;
+    if (graph_ptr) {   // (graph_rows, on the host)
+      const int lo = imin(imax(graph_ptr[gi], 0), n_total), hi = imin(imax(graph_ptr[gi + 1], 0), n_total);
+      g0 = lo;
+      n = hi - lo;
+    }
+    unsigned bb[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    for (int r = g0; r < g0 + n; ++r) {
+      const float* p = x + (size_t)r * 3;
+      if (!cell_finite(p[0], p[1], p[2])) continue;
+      for (int a = 0; a < 3; ++a) {
+        const unsigned key = cell_key(p[a]);
+        if (~key > bb[a]) bb[a] = ~key;
+        if (key > bb[3 + a]) bb[3 + a] = key;
+      }
+    }
+    const CellGrid cg = cell_grid(bb, n, rr);
+    if (grid) grid[gi] = cg.g;
+    if (box)
+      for (int a = 0; a < 3; ++a) {
+        box[gi * 9 + a] = cg.lo[a];
+        box[gi * 9 + 3 + a] = cg.hi[a];
+        box[gi * 9 + 6 + a] = cg.inv_w[a];
+      }
+    for (int r = g0; r < g0 + n; ++r) {
+      const float* p = x + (size_t)r * 3;
+      const bool fin = cell_finite(p[0], p[1], p[2]);
+      const CellBox bx = fin ? cell_box(cg, p[0], p[1], p[2], rr) : CellBox{{-1, -1, -1}, {-1, -1, -1}};
+      for (int a = 0; a < 3; ++a) {
+        if (cell) cell[(size_t)r * 3 + a] = fin ? cell_of(p[a], cg.lo[a], cg.inv_w[a], cg.g) : -1;
+        if (range) {
+          range[(size_t)r * 6 + a] = bx.lo[a];
+          range[(size_t)r * 6 + 3 + a] = bx.hi[a];
+        }
+      }
+    }
+  }
+  return NONODE_OK;
 }
 
 size_t nonode_neighbor_by_sender_workspace_bytes(long long cap, int n_total) {

@@ -33,7 +33,10 @@ segment (harness.egno_rollout_graph / segno_rollout_graph). Built with ``by_send
 ``NeighborGraph.with_sender_csr()``) it also carries the CSR by sender and the tail mask of the reverse pass,
 made on the device from the padded list (``nonode_neighbor_by_sender``), so EGNO(graph="trainable") and
 SEGNO(graph="any", trainable=True) train on it with nothing read back (harness.egno_rollout_train_graph /
-segno_rollout_train_graph unroll a rollout on such graphs).
+segno_rollout_train_graph unroll a rollout on such graphs). Under a finite cut-off the builder can search a cell
+list instead of all the nodes of a graph (``method="cells"``, ``nonode_neighbor_graph_cells``): the same arrays bit
+for bit, O(cells the cut-off box touches) per receiver instead of O(N); ``method="auto"`` chooses by the size of
+the largest graph (``neighbor_method``).
 
 Graphs of mixed sizes in one batch (``RaggedBatch``, ``neighbor_graph_ragged``): the descriptor holds the sizes
 on the host and their prefix sum and node -> graph map on the device, uploaded once; the builder, the node
@@ -409,6 +412,39 @@ def neighbor_args(k, r_cut):
     return k, r2
 
 
+# method="auto": the size of the largest graph from which the cell-list search is taken under a finite cut-off.
+# Measured (profiles/graph/bench_cells.jsonl): the smallest measured N at which the
+# cell list beat the brute-force search in every alternation, as it did at every larger measured N.
+# Measured on the MI355X at about 12 candidates per receiver, k = 16: 10,000 (1.38 x there; the brute-force search
+# is the faster one at 4,000 and below, where the cell list's five extra launches cost more than the search saves).
+# None would mean not measured, and "auto" would be "brute".
+CELLS_AUTO_MIN_NODES = 10000
+
+
+def neighbor_method(method, r_cut, n_max=0):
+    """The search a neighbour-graph build runs, "brute" or "cells", from its method= argument, on the host and
+    before any device work. None / "brute": one wave per receiver over all the nodes of its graph (any r_cut).
+    "cells": the cell-list search, which needs a cut-off whose float32 square is finite (ValueError otherwise);
+    the same arrays, bit for bit. "auto": "cells" when such a cut-off is given and the largest graph has at
+    least CELLS_AUTO_MIN_NODES nodes, else "brute". Anything else: ValueError."""
+    if method is None or method == "brute":
+        return "brute"
+    if method not in ("cells", "auto"):
+        raise ValueError(f'neighbor_graph: method must be None, "brute", "cells" or "auto", got {method!r}')
+    finite = False
+    if r_cut is not None:
+        with np.errstate(over="ignore"):
+            finite = bool(np.isfinite(np.float32(r_cut) * np.float32(r_cut)))
+    if method == "auto":
+        return "cells" if finite and CELLS_AUTO_MIN_NODES is not None and n_max >= CELLS_AUTO_MIN_NODES else "brute"
+    if r_cut is None:
+        raise ValueError('neighbor_graph: method="cells" needs a cut-off (r_cut=None is the pure k-NN graph, which '
+                         "only the brute-force search builds)")
+    if not finite:
+        raise ValueError(f'neighbor_graph: method="cells" needs a finite float32(r_cut)^2, got r_cut = {r_cut!r}')
+    return "cells"
+
+
 def _sender_csr(rows, col, row_ptr):
     """(srow_ptr, seid, valid) of a device-built graph: nonode_neighbor_by_sender on the padded list and its
     device-side count, on the stream of `rows`."""
@@ -427,7 +463,7 @@ def _sender_csr(rows, col, row_ptr):
     return srow_ptr, seid, valid
 
 
-def neighbor_graph(x, batch_size, n_nodes, k, r_cut=None, *, by_sender=False):
+def neighbor_graph(x, batch_size, n_nodes, k, r_cut=None, *, by_sender=False, method=None):
     """The k-nearest-neighbour graph (with r_cut: among the nodes within r_cut) of x [B N, 3], B = batch_size
     graphs of N = n_nodes consecutive rows, as a NeighborGraph: one nonode_neighbor_graph call, asynchronous,
     nothing read back. Receiver i keeps the min(k, candidates) nodes j != i of its graph with the smallest
@@ -436,20 +472,24 @@ def neighbor_graph(x, batch_size, n_nodes, k, r_cut=None, *, by_sender=False):
     is a pure function of the positions, bitwise the same from run to run. k in [1, 64].
     by_sender=True also builds the CSR by sender (NeighborGraph.srow_ptr, seid, valid: one
     nonode_neighbor_by_sender call on the same stream), which training on the graph needs. The graph is a
-    discrete function of x: nothing here is differentiable, and no gradient flows through it."""
+    discrete function of x: nothing here is differentiable, and no gradient flows through it.
+    method (neighbor_method): None / "brute" searches all N nodes per receiver; "cells" (a finite cut-off only)
+    searches a cell list instead, one nonode_neighbor_graph_cells call, and returns the same arrays bit for bit,
+    faster on large graphs; "auto" chooses by the size."""
     from . import _lib
     B, N = int(batch_size), int(n_nodes)
     k, r2 = neighbor_args(k, r_cut)
+    method = neighbor_method(method, r_cut, N)
     if B < 1 or N < 1 or x.dim() != 2 or tuple(x.shape) != (B * N, 3):
         raise ValueError(f"neighbor_graph: x must be [batch_size * n_nodes, 3] = [{B * N}, 3], got {tuple(x.shape)}")
     _lib.require_device(x)
-    return _build_neighbor_graph(x, k, r2, by_sender, B, N, None)
+    return _build_neighbor_graph(x, k, r2, by_sender, B, N, None, method)
 
 
-def _build_neighbor_graph(x, k, r2, by_sender, B, N, batch):
+def _build_neighbor_graph(x, k, r2, by_sender, B, N, batch, method="brute"):
     """The builder's call behind neighbor_graph (B graphs of N rows; batch None) and neighbor_graph_ragged
     (batch a RaggedBatch; B, N unused), after their host checks: outputs, workspace, one C call, and the CSR
-    by sender if asked."""
+    by sender if asked. method "cells": the cell-list entry (equal sizes: null descriptors) in place of either."""
     from . import _lib
     x = _lib.f32(x)
     dev = x.device
@@ -458,7 +498,14 @@ def _build_neighbor_graph(x, k, r2, by_sender, B, N, batch):
     col, eid, rows = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
     L = _lib.lib()
     out = (_lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(eid), _lib.ptr(rows))
-    if batch is None:
+    if method == "cells":
+        G, n_max = (B, N) if batch is None else (batch.n_graphs, batch.n_max)
+        desc = (None, None) if batch is None else (batch.graph_ptr, batch.graph_of)
+        ws_bytes = L.nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k)
+        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+        _lib.check(L.nonode_neighbor_graph_cells(G, n_total, n_max, k, cap, r2, _lib.ptr(desc[0]), _lib.ptr(desc[1]),
+                                                 _lib.ptr(x), *out, _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
+    elif batch is None:
         ws_bytes = L.nonode_neighbor_graph_workspace_bytes(B, N, k)
         ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
         _lib.check(L.nonode_neighbor_graph(B, N, k, r2, _lib.ptr(x), *out, _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
@@ -527,18 +574,20 @@ def as_batch(sizes, device):
     return RaggedBatch(sizes, device)
 
 
-def neighbor_graph_ragged(x, batch, k, r_cut=None, *, by_sender=False):
+def neighbor_graph_ragged(x, batch, k, r_cut=None, *, by_sender=False, method=None):
     """neighbor_graph for a batch of mixed sizes: x [n_total, 3], batch a RaggedBatch (or a host sequence of
     sizes, wrapped: repeated callers pass the RaggedBatch). Receiver r of graph g keeps the min(k, N_g - 1,
     candidates) nodes j != r of its own graph with the smallest (d2, j), d2 and the candidates as in
     neighbor_graph; a graph of one node has rows of degree 0. One nonode_neighbor_graph_ragged call,
     asynchronous, nothing read back; bitwise a pure function of the positions and the sizes, and for equal
     sizes bitwise neighbor_graph's arrays. The NeighborGraph has n_nodes None, batch the descriptor and
-    capacity == batch.capacity(k)."""
+    capacity == batch.capacity(k). method as in neighbor_graph ("auto" goes by the largest graph)."""
     from . import _lib
     k, r2 = neighbor_args(k, r_cut)
+    neighbor_method(method, r_cut)
     if not isinstance(batch, RaggedBatch):
         batch = RaggedBatch(batch, x.device)
+    method = neighbor_method(method, r_cut, batch.n_max)
     if x.dim() != 2 or tuple(x.shape) != (batch.n_total, 3):
         raise ValueError(f"neighbor_graph_ragged: x must be [n_total, 3] = [{batch.n_total}, 3], got {tuple(x.shape)}")
     _lib.require_device(x, batch.graph_ptr)
@@ -546,7 +595,7 @@ def neighbor_graph_ragged(x, batch, k, r_cut=None, *, by_sender=False):
         raise ValueError(f"neighbor_graph_ragged: the RaggedBatch lives on {batch.device}, x on {x.device}")
     if batch.capacity(k) >= 2 ** 31:
         raise ValueError(f"neighbor_graph_ragged: capacity {batch.capacity(k)} (must be < 2^31)")
-    return _build_neighbor_graph(x, k, r2, by_sender, 0, 0, batch)
+    return _build_neighbor_graph(x, k, r2, by_sender, 0, 0, batch, method)
 
 
 # the second CSR of the reverse pass (EGNO graph="trainable"), cached per edge tensor pair like _csr

@@ -406,19 +406,22 @@ def _segno_rollout_multi(model, h, loc, edge_index, vel, edge_attr, traj_len, nu
 
 # ---- general graphs: featurisation on an explicit list, rollouts on k-NN / cut-off graphs ----
 
-def _graph_source(k, r_cut, edges, who):
+def _graph_source(k, r_cut, edges, who, neighbor_method=None):
     if (k is None) == (edges is None):
         raise ValueError(f"{who}: give exactly one of k (a neighbour graph built from the positions, with an "
                          "optional r_cut) and edges (a fixed list)")
     if edges is not None and r_cut is not None:
         raise ValueError(f"{who}: r_cut goes with k (a fixed edge list has no cut-off)")
+    if edges is not None and neighbor_method is not None:
+        raise ValueError(f"{who}: neighbor_method goes with k (a fixed edge list is not searched for)")
     if k is not None:
-        from .graph import neighbor_args
-        neighbor_args(k, r_cut)
+        from . import graph as _graph
+        _graph.neighbor_args(k, r_cut)
+        _graph.neighbor_method(neighbor_method, r_cut)
 
 
 def prepare_inputs_graph(loc, vel, n_nodes, charges=None, t_in=None, *, k=None, r_cut=None, edges=None, tape=False,
-                         sizes=None):
+                         sizes=None, neighbor_method=None):
     """prepare_inputs (main_simulation_simple_no.py:311-339, num_inputs == 1) on an explicit edge list
     instead of the implicit fully connected one. loc, vel: [B, N, 3] or [F, B, N, 3] with t_in [B] choosing
     frame t_in - 1 per sample (a python index taken modulo F on the device, as nonode_prepare_inputs takes it:
@@ -441,7 +444,11 @@ def prepare_inputs_graph(loc, vel, n_nodes, charges=None, t_in=None, *, k=None, 
     sizes (a graph.RaggedBatch, or a host sequence of sizes, wrapped; n_nodes must then be None): G graphs of
     mixed sizes. loc, vel [n_total, 3] or [F, n_total, 3], t_in one value per graph, charges n_total values;
     the mean is each graph's own, k builds through graph.neighbor_graph_ragged, and the tape's reverse is
-    nonode_prepare_inputs_bwd_ragged. Same returns."""
+    nonode_prepare_inputs_bwd_ragged. Same returns.
+
+    neighbor_method (with k only): the search that builds the graph, graph.neighbor_graph's method= (None /
+    "brute", "cells" under a finite r_cut, "auto"): the same graph bit for bit, built faster on large graphs."""
+    _graph_source(k, r_cut, edges, "prepare_inputs_graph", neighbor_method)
     batch = None
     if sizes is not None:
         if n_nodes is not None:
@@ -450,10 +457,12 @@ def prepare_inputs_graph(loc, vel, n_nodes, charges=None, t_in=None, *, k=None, 
         batch = as_batch(sizes, loc.device)
     if tape and torch.is_grad_enabled() and (loc.requires_grad or vel.requires_grad):
         box = []
-        x, v, lm, ea, nodes = _PrepareInputsGraph.apply(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, box, batch)
+        x, v, lm, ea, nodes = _PrepareInputsGraph.apply(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, box, batch,
+                                                        neighbor_method)
         return x, v, ea, nodes, lm, box[0]
     with torch.no_grad():
-        return _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, bool(tape), batch)
+        return _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, bool(tape), batch,
+                                     neighbor_method)
 
 
 class _PrepareInputsGraph(torch.autograd.Function):
@@ -461,8 +470,9 @@ class _PrepareInputsGraph(torch.autograd.Function):
     explicit list. The graph (not a tensor) leaves through `box`."""
 
     @staticmethod
-    def forward(ctx, loc, vel, n_nodes, charges, t_in, k, r_cut, edges, box, batch):
-        x, v, ea, nodes, lm, g = _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, True, batch)
+    def forward(ctx, loc, vel, n_nodes, charges, t_in, k, r_cut, edges, box, batch, method=None):
+        x, v, ea, nodes, lm, g = _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, True, batch,
+                                                       method)
         box.append(g)
         ctx.batch = batch
         ctx.shape, ctx.dtypes = tuple(loc.shape), (loc.dtype, vel.dtype)
@@ -473,13 +483,13 @@ class _PrepareInputsGraph(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gx, gv, glm, _gea, _gnodes):
-        return _PrepareInputs.backward(ctx, gx, gv, glm, _gea, _gnodes) + (None, None, None)
+        return _PrepareInputs.backward(ctx, gx, gv, glm, _gea, _gnodes) + (None, None, None, None)
 
 
-def _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, by_sender, batch=None):
+def _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, by_sender, batch=None, method=None):
     """prepare_inputs_graph off the tape (callers hold torch.no_grad()). batch: a RaggedBatch or None."""
     from . import graph as _graph
-    _graph_source(k, r_cut, edges, "prepare_inputs_graph")
+    _graph_source(k, r_cut, edges, "prepare_inputs_graph", method)
     if batch is None:
         if loc.dim() not in (3, 4) or loc.shape != vel.shape or loc.shape[-1] != 3:
             raise ValueError(f"prepare_inputs_graph: loc, vel must be [B, N, 3] or [F, B, N, 3] alike, got "
@@ -525,8 +535,8 @@ def _prepare_inputs_graph(loc, vel, n_nodes, charges, t_in, k, r_cut, edges, by_
     else:
         _lib.check(L.nonode_prepare_nodes_ragged(B, BN, F, _lib.ptr(batch.graph_ptr), *io))
     if edges is None:
-        edges = (_graph.neighbor_graph(x, B, N, k, r_cut, by_sender=by_sender) if batch is None else
-                 _graph.neighbor_graph_ragged(x, batch, k, r_cut, by_sender=by_sender))
+        edges = (_graph.neighbor_graph(x, B, N, k, r_cut, by_sender=by_sender, method=method) if batch is None else
+                 _graph.neighbor_graph_ragged(x, batch, k, r_cut, by_sender=by_sender, method=method))
         rows, cols = edges.rows, edges.col
     n_edges = edges.n_edges if isinstance(edges, _graph.NeighborGraph) else None
     rows, cols = rows.contiguous(), cols.contiguous()
@@ -603,7 +613,8 @@ def _segno_layout(who, loc, vel, batch_size, sizes):
 
 @torch.no_grad()
 def egno_rollout_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, *, k=None, r_cut=None, edges=None,
-                       timesteps_in=None, timesteps_out=None, energy_dataset=None, return_graphs=False, sizes=None):
+                       timesteps_in=None, timesteps_out=None, energy_dataset=None, return_graphs=False, sizes=None,
+                       neighbor_method=None):
     """rollout_fn (main_simulation_simple_no.py:342-384), num_inputs == 1, on a general graph, as a loop of
     model(...) segments like _egno_rollout_segments. loc, vel [B, N, 3]. Per segment: prepare_inputs_graph
     on the current frame (k: the neighbour graph is rebuilt from that frame on the device; edges: the
@@ -613,14 +624,15 @@ def egno_rollout_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, 
     does, and with return_graphs=True also the list of the segments' graphs.
     sizes (a graph.RaggedBatch or a host sequence; n_nodes and batch_size None): G graphs of mixed sizes in
     the one loop. loc, vel [n_total, 3], timesteps_in [G], timesteps_out shared (one row); loc_preds
-    [traj_len*T, n_total, 3], energies [.., G, 1]."""
+    [traj_len*T, n_total, 3], energies [.., G, 1].
+    neighbor_method (with k): the search behind every segment's graph, as in prepare_inputs_graph."""
     from .egno import EGNO
     _general_model(model, EGNO, "egno_rollout_graph")
     if model.num_inputs > 1:
         raise NotImplementedError("egno_rollout_graph rolls the single-input model out (num_inputs == 1)")
     if model.flat:
         raise NotImplementedError("egno_rollout_graph does not run with flat=True (general graphs)")
-    _graph_source(k, r_cut, edges, "egno_rollout_graph")
+    _graph_source(k, r_cut, edges, "egno_rollout_graph", neighbor_method)
     T = model.num_timesteps
     lay = _Layout("egno_rollout_graph", loc, n_nodes, batch_size, sizes)
     lay.first("egno_rollout_graph", loc, vel)
@@ -638,7 +650,8 @@ def egno_rollout_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, 
     ti = timesteps_in.reshape(-1) if timesteps_in is not None else None   # None: the last frame (t_in = T)
     preds = torch.empty(traj_len * T, BN, 3, device=dev)
     en_all, graphs = [], []
-    x, v, edge_attr, nodes, loc_mean, g = lay.prepare(loc, vel, charges, k=k, r_cut=r_cut, edges=edges)
+    x, v, edge_attr, nodes, loc_mean, g = lay.prepare(loc, vel, charges, k=k, r_cut=r_cut, edges=edges,
+                                                      neighbor_method=neighbor_method)
     for i in range(traj_len):
         graphs.append(g)
         t_out = timesteps_out[:, i * T:(i + 1) * T] - i * T
@@ -648,7 +661,8 @@ def egno_rollout_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, 
             en_all.append(lay.energy(energy_dataset, x.reshape(T, BN, 3), v.reshape(T, BN, 3), charges))
         if i + 1 < traj_len:
             x, v, edge_attr, nodes, loc_mean, g = lay.prepare(lay.frames(x, T), lay.frames(v, T), charges, ti, k=k,
-                                                              r_cut=r_cut, edges=edges)
+                                                              r_cut=r_cut, edges=edges,
+                                                              neighbor_method=neighbor_method)
     tail = (graphs,) if return_graphs else ()
     if energy_dataset is None:
         return (preds, None, None) + tail
@@ -657,7 +671,8 @@ def egno_rollout_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, 
 
 
 def egno_rollout_train_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, *, k=None, r_cut=None,
-                             edges=None, timesteps_in=None, timesteps_out=None, return_graphs=False, sizes=None):
+                             edges=None, timesteps_in=None, timesteps_out=None, return_graphs=False, sizes=None,
+                             neighbor_method=None):
     """The loop of egno_rollout_graph on the autograd tape (unrolled rollout training on a general graph),
     num_inputs == 1, for a model built with graph="trainable". loc, vel [B, N, 3]. Per segment:
     prepare_inputs_graph(tape=True) on the selected frame (k: the neighbour graph, with its CSR by sender, is
@@ -668,7 +683,7 @@ def egno_rollout_train_graph(model, loc, vel, charges, n_nodes, batch_size, traj
     nodes / edge_attr (detached, as the reference does at main_simulation_simple_no.py:333,338). No
     energies. Nothing in the loop or in the backward reads the device.
     sizes: G graphs of mixed sizes, as in egno_rollout_graph (loc, vel [n_total, 3], timesteps_in [G], shared
-    timesteps_out; the per-graph mean and its reverse are each graph's own)."""
+    timesteps_out; the per-graph mean and its reverse are each graph's own). neighbor_method as there."""
     from . import graph as _graph
     from .egno import EGNO
     who = "egno_rollout_train_graph"
@@ -680,7 +695,7 @@ def egno_rollout_train_graph(model, loc, vel, charges, n_nodes, batch_size, traj
         raise NotImplementedError(f"{who} unrolls the single-input model (num_inputs == 1)")
     if model.flat:
         raise NotImplementedError(f"{who} does not run with flat=True (general graphs)")
-    _graph_source(k, r_cut, edges, who)
+    _graph_source(k, r_cut, edges, who, neighbor_method)
     T = model.num_timesteps
     lay = _Layout(who, loc, n_nodes, batch_size, sizes)
     lay.first(who, loc, vel)
@@ -699,7 +714,8 @@ def egno_rollout_train_graph(model, loc, vel, charges, n_nodes, batch_size, traj
     preds, graphs = [], []
     x, v, t_in = loc, vel, None
     for i in range(traj_len):
-        x, v, edge_attr, nodes, loc_mean, g = lay.prepare(x, v, charges, t_in, k=k, r_cut=r_cut, edges=edges, tape=True)
+        x, v, edge_attr, nodes, loc_mean, g = lay.prepare(x, v, charges, t_in, k=k, r_cut=r_cut, edges=edges, tape=True,
+                                                          neighbor_method=neighbor_method)
         graphs.append(g)
         t_out = timesteps_out[:, i * T:(i + 1) * T] - i * T
         x, v, _ = model(x, nodes, g, edge_attr, v=v, loc_mean=loc_mean, timesteps_out=t_out)
@@ -711,7 +727,7 @@ def egno_rollout_train_graph(model, loc, vel, charges, n_nodes, batch_size, traj
 
 @torch.no_grad()
 def segno_rollout_graph(model, loc, vel, charges, batch_size, traj_len, num_steps=10, *, k=None, r_cut=None,
-                        edges=None, energy_dataset=None, return_graphs=False, sizes=None):
+                        edges=None, energy_dataset=None, return_graphs=False, sizes=None, neighbor_method=None):
     """rollout_fn (train_nbody.py:200-236), num_prev == 1, on a general graph, as a loop of model(...)
     segments. loc, vel [BN, 3]; his = |v|; num_steps an int or a list of length traj_len. The graph (k:
     rebuilt on the device; edges: fixed) and the edge attributes [q_r q_c, |x_r - x_c|^2] come from each
@@ -719,12 +735,13 @@ def segno_rollout_graph(model, loc, vel, charges, batch_size, traj_len, num_step
     the loop reads the device. Returns (loc_preds [traj_len, BN, 3], energies [traj_len, B, 1] or None), and
     with return_graphs=True also the list of the segments' graphs.
     sizes (a graph.RaggedBatch or a host sequence; batch_size None or len(sizes)): G graphs of mixed sizes in
-    the one loop. loc, vel [n_total, 3]; energies [traj_len, G, 1]."""
+    the one loop. loc, vel [n_total, 3]; energies [traj_len, G, 1].
+    neighbor_method (with k): the search behind every segment's graph, as in prepare_inputs_graph."""
     from .segno import SEGNO
     _general_model(model, SEGNO, "segno_rollout_graph")
     if model.bug_compat:
         raise ValueError("segno_rollout_graph integrates (bug_compat=True would return the inputs every segment)")
-    _graph_source(k, r_cut, edges, "segno_rollout_graph")
+    _graph_source(k, r_cut, edges, "segno_rollout_graph", neighbor_method)
     lay = _segno_layout("segno_rollout_graph", loc, vel, batch_size, sizes)
     steps = list(num_steps) if isinstance(num_steps, (list, tuple)) else [int(num_steps)] * traj_len
     if len(steps) != traj_len:
@@ -734,7 +751,8 @@ def segno_rollout_graph(model, loc, vel, charges, batch_size, traj_len, num_step
     en, graphs = [], []
     x, v = loc, vel
     for i, T in enumerate(steps):
-        x, v, edge_attr, nodes, _, g = lay.prepare(lay.frames(x), lay.frames(v), charges, k=k, r_cut=r_cut, edges=edges)
+        x, v, edge_attr, nodes, _, g = lay.prepare(lay.frames(x), lay.frames(v), charges, k=k, r_cut=r_cut, edges=edges,
+                                                   neighbor_method=neighbor_method)
         graphs.append(g)
         x, _, v = model(nodes[:, :1], x, g, v, edge_attr, T=int(T))
         preds[i] = x
@@ -745,7 +763,7 @@ def segno_rollout_graph(model, loc, vel, charges, batch_size, traj_len, num_step
 
 
 def segno_rollout_train_graph(model, loc, vel, charges, batch_size, traj_len, num_steps=10, *, k=None, r_cut=None,
-                              edges=None, return_graphs=False, sizes=None):
+                              edges=None, return_graphs=False, sizes=None, neighbor_method=None):
     """The loop of segno_rollout_graph on the autograd tape (unrolled rollout training on a general graph),
     num_prev == 1, for a model built with graph="any", trainable=True. loc, vel [BN, 3]; num_steps an int or a
     list of length traj_len. Per segment: prepare_inputs_graph(tape=True) on the previous segment's predicted
@@ -755,7 +773,7 @@ def segno_rollout_train_graph(model, loc, vel, charges, batch_size, traj_len, nu
     to the parameters and to the initial loc and vel. No gradient flows through the choice of neighbours (it is
     discrete) or through his = |v| and edge_attr (detached: the reference builds them from data,
     train_nbody.py:121-123,230-233, as egno_rollout_train_graph does). No energies. Nothing in the loop or in
-    the backward reads the device. sizes: G graphs of mixed sizes, as in segno_rollout_graph."""
+    the backward reads the device. sizes: G graphs of mixed sizes, and neighbor_method, as in segno_rollout_graph."""
     from . import graph as _graph
     from .segno import SEGNO
     who = "segno_rollout_train_graph"
@@ -766,7 +784,7 @@ def segno_rollout_train_graph(model, loc, vel, charges, batch_size, traj_len, nu
                          f"trainable={model.trainable!r}")
     if model.bug_compat:
         raise ValueError(f"{who} integrates (bug_compat=True would return the inputs every segment)")
-    _graph_source(k, r_cut, edges, who)
+    _graph_source(k, r_cut, edges, who, neighbor_method)
     lay = _segno_layout(who, loc, vel, batch_size, sizes)
     steps = list(num_steps) if isinstance(num_steps, (list, tuple)) else [int(num_steps)] * traj_len
     if len(steps) != traj_len:
@@ -778,7 +796,7 @@ def segno_rollout_train_graph(model, loc, vel, charges, batch_size, traj_len, nu
     x, v = loc, vel
     for T in steps:
         x, v, edge_attr, nodes, _, g = lay.prepare(lay.frames(x), lay.frames(v), charges, k=k, r_cut=r_cut,
-                                                   edges=edges, tape=True)
+                                                   edges=edges, tape=True, neighbor_method=neighbor_method)
         graphs.append(g)
         x, _, v = model(nodes[:, :1].detach(), x, g, v, edge_attr.detach(), T=int(T))
         preds.append(x)

@@ -1,0 +1,350 @@
+"""GPU tests of the cell-list search for cut-off neighbour graphs (graph.neighbor_graph / neighbor_graph_ragged
+with method="cells", nonode_neighbor_graph_cells).
+
+The contract is the brute-force builder's, bit for bit, so there is no tolerance anywhere here: every array is
+compared with np.array_equal against the numpy restatements tests/_neighbor_ref.py / tests/_ragged_ref.py (the
+builder's float32 arithmetic taken literally) and with torch.equal against method="brute" on the same device.
+Rollouts and models on a cells-built graph are compared with torch.equal to the same call on the brute-built
+one. Each reference is computed once per case.
+"""
+import numpy as np
+import pytest
+import torch
+
+import no_node_comparison_amd as pkg
+from no_node_comparison_amd import graph, harness
+from tests._neighbor_ref import cutoff_straddlers, d2_unfused, neighbor_ref, tied_pairs
+from tests._ragged_ref import ragged_neighbor_ref
+from tests.conftest import load_golden, params_of
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+NAMES = ("row_ptr", "col", "rows", "eid")
+
+
+def _dev(a):
+    return torch.tensor(np.ascontiguousarray(a)).to(DEV)
+
+
+def _points(n, seed, scale=1.5):
+    return (np.random.RandomState(seed).randn(n, 3) * scale).astype(np.float32)
+
+
+def _both(x, B, N, k, r_cut, **kw):
+    xd = _dev(x)
+    a = graph.neighbor_graph(xd, B, N, k, r_cut, method="brute", **kw)
+    b = graph.neighbor_graph(xd, B, N, k, r_cut, method="cells", **kw)
+    torch.cuda.synchronize()
+    return a, b
+
+
+def _same_graph(a, b, sender=False):
+    for n in NAMES + (("srow_ptr", "seid", "valid") if sender else ()):
+        assert torch.equal(getattr(a, n), getattr(b, n)), n
+    assert a.capacity == b.capacity and a.n_nodes == b.n_nodes
+
+
+def _assert_ref(ng, ref):
+    got = {n: getattr(ng, n).cpu().numpy() for n in NAMES}
+    E = int(got["row_ptr"][-1])
+    assert ng.capacity == ref["cap"] and E == ref["E"]
+    for n in NAMES:
+        assert got[n].dtype == np.int32 and got[n].shape == ref[n].shape, n
+        assert np.array_equal(got[n], ref[n]), n
+    assert np.all(got["col"][E:] == -1) and np.all(got["rows"][E:] == -1)
+
+
+def _check(x, B, N, k, r_cut):
+    """cells == brute == the numpy reference; returns the reference."""
+    ref = neighbor_ref(x, B, N, k, r_cut)
+    a, b = _both(x, B, N, k, r_cut)
+    _same_graph(a, b)
+    _assert_ref(b, ref)
+    return ref
+
+
+# ---- 1. bitwise against the references ---------------------------------------------------------------------
+@pytest.mark.parametrize("B,N,r_cut,empty,full", [(2, 1000, 0.6, 224, 55), (1, 2000, 0.5, 206, 115)])
+def test_cells_match_the_numpy_reference_with_empty_and_truncated_rows(B, N, r_cut, empty, full):
+    """Seed 11 Gaussian x 1.5, k = 16: rows without a candidate and rows cut at k, in known numbers."""
+    ref = _check(_points(B * N, 11), B, N, 16, r_cut)
+    assert int((ref["deg"] == 0).sum()) == empty and int((ref["deg"] == 16).sum()) == full
+    assert ref["E"] < ref["cap"]
+
+
+@pytest.mark.parametrize("B,N,k,r_cut", [(3, 200, 8, 0.9), (1, 65, 64, 1.2)])
+def test_cells_match_the_numpy_reference_on_small_batches(B, N, k, r_cut):
+    ref = _check(_points(B * N, 11), B, N, k, r_cut)
+    assert (ref["deg"] == 0).any() and ref["E"] > 0
+    if k < N - 1:
+        assert (ref["deg"] == k).any()             # empty and truncated rows (k = 64 = N - 1 cuts nothing)
+
+
+@pytest.mark.parametrize("N", [1, 2, 63, 64, 65])
+def test_cells_at_the_sizes_around_a_wave(N):
+    ref = _check(_points(2 * N, 5), 2, N, 16, 1.5)
+    if N == 1:
+        assert ref["E"] == 0 and ref["cap"] == 0
+    else:
+        assert ref["E"] > 0
+
+
+def test_a_cut_off_wider_than_the_cloud_and_one_below_every_distance():
+    x = _points(300, 7)
+    ref = _check(x, 1, 300, 16, 100.0)                  # one cell: every row is the 16 nearest
+    assert np.all(ref["deg"] == 16)
+    ref = _check(x, 1, 300, 16, 1e-4)                   # no pair within the cut-off: all rows empty
+    assert ref["E"] == 0
+
+
+# ---- 2. adversarial inputs -----------------------------------------------------------------------------------
+def _lattice8():
+    return np.stack(np.meshgrid(*[np.arange(8)] * 3, indexing="ij"), -1).reshape(-1, 3).astype(np.float32)
+
+
+@pytest.mark.parametrize("r_cut,k", [(1.0, 16), (2.0, 16), (1.5, 16), (2.0, 64)])
+def test_cells_on_a_lattice(r_cut, k):
+    """Ties at the cut-off and at the k-th place, nodes on cell faces (8^3 nodes: g = 5, width 1.4)."""
+    ref = _check(_lattice8(), 1, 512, k, r_cut)
+    assert ref["deg"].max() == {1.0: 6, 1.5: 16, 2.0: min(k, 32)}[r_cut] and ref["deg"].min() >= 3
+
+
+def test_cells_with_coincident_nodes():
+    x = _points(400, 3)
+    x[100:200] = x[7]
+    ref = _check(x, 1, 400, 16, 0.6)
+    assert np.all(ref["deg"][100:200] == 16)
+    _check(np.repeat(x[:1], 130, 0), 2, 65, 8, 0.5)     # zero extent on every axis
+
+
+def test_cells_with_a_nan_and_an_inf_coordinate():
+    x = (np.random.RandomState(4).rand(600, 3) * 8).astype(np.float32)
+    x[40, 1], x[300 + 77, 0], x[300 + 78, 2] = np.nan, np.inf, -np.inf
+    ref = _check(x, 2, 300, 16, 1.5)
+    for r in (40, 377, 378):
+        assert ref["deg"][r] == 0 and r not in ref["col"]
+    assert ref["E"] > 0
+
+
+def test_cells_with_large_positions_and_extents():
+    x = _points(600, 6)
+    _check(x * np.float32(1e8), 2, 300, 16, 0.8e8)
+    far = (np.random.RandomState(8).rand(300, 3) * 8).astype(np.float32)
+    far[3], far[250] = 3e38, -3e38                      # the extent overflows: one cell, still the same graph
+    ref = _check(far, 1, 300, 16, 1.5)
+    assert ref["deg"][3] == 0 and ref["deg"][250] == 0 and ref["E"] > 0
+    out = (np.random.RandomState(9).rand(1000, 3) * 10).astype(np.float32)
+    out[17] = 1e4                                       # one outlier stretches every axis
+    ref = _check(out, 1, 1000, 16, 1.5)
+    assert ref["deg"][17] == 0
+    lng = (np.random.RandomState(10).rand(1000, 3) * np.array([100, 0.01, 0.01])).astype(np.float32)
+    assert _check(lng, 1, 1000, 16, 0.5)["E"] > 0      # elongated 100 : 0.01 : 0.01
+
+
+def test_cells_do_not_contract_the_distance():
+    """tests/_neighbor_ref.py's senders whose individually rounded d2 tie, or meet float32(r_cut)^2, while the
+    contracted ones do not: the cell search computes the same dist2."""
+    pairs = tied_pairs(16)
+    G = len(pairs)
+    x = np.zeros((G, 3, 3), dtype=np.float32)
+    for g, (a, b) in enumerate(pairs):
+        x[g, 1], x[g, 2] = a, b
+    x = x.reshape(-1, 3)
+    ref = _check(x, G, 3, 1, 4.0)
+    assert all(ref["col"][ref["row_ptr"][3 * g]] == 3 * g + 1 for g in range(G))   # the tie goes to the lower index
+    for pt, r_cut, cand in cutoff_straddlers(2):
+        xs = np.stack([np.zeros(3, dtype=np.float32), pt])
+        assert (d2_unfused(pt) <= np.float32(r_cut) * np.float32(r_cut)) == cand
+        assert _check(xs, 1, 2, 1, r_cut)["E"] == (2 if cand else 0)
+
+
+# ---- 3. mixed sizes ---------------------------------------------------------------------------------------------
+SIZES = [1, 2, 37, 250, 1000]
+
+
+def test_cells_on_mixed_sizes_match_the_ragged_reference():
+    n = sum(SIZES)
+    x = (np.random.RandomState(11).rand(n, 3) * 6).astype(np.float32)
+    x[1 + 2 + 5, 0] = np.nan
+    ref = ragged_neighbor_ref(x, SIZES, 16, 1.0)
+    assert (ref["deg"] == 0).any() and (ref["deg"] == 16).any() and ref["E"] < ref["cap"]
+    xd = _dev(x)
+    batch = graph.RaggedBatch(SIZES, xd.device)
+    a = graph.neighbor_graph_ragged(xd, batch, 16, 1.0, method="brute", by_sender=True)
+    b = graph.neighbor_graph_ragged(xd, batch, 16, 1.0, method="cells", by_sender=True)
+    torch.cuda.synchronize()
+    _same_graph(a, b, sender=True)
+    _assert_ref(b, ref)
+    assert b.n_nodes is None and b.batch is batch
+
+
+def test_equal_sizes_as_a_ragged_batch_and_by_sender():
+    B, N = 3, 200
+    x = _points(B * N, 11)
+    xd = _dev(x)
+    eq = graph.neighbor_graph(xd, B, N, 8, 0.9, method="cells", by_sender=True)
+    rg = graph.neighbor_graph_ragged(xd, [N] * B, 8, 0.9, method="cells", by_sender=True)
+    br = graph.neighbor_graph(xd, B, N, 8, 0.9, method="brute", by_sender=True)
+    torch.cuda.synchronize()
+    for n in NAMES + ("srow_ptr", "seid", "valid"):
+        assert torch.equal(getattr(eq, n), getattr(rg, n)), n
+        assert torch.equal(getattr(eq, n), getattr(br, n)), n
+    assert 0 < int(eq.n_edges.item()) < eq.capacity
+
+
+# ---- 4. one large graph, determinism -----------------------------------------------------------------------------
+def test_one_graph_of_20000_nodes_equals_brute_and_repeats_bitwise():
+    """The uniform cube of tools/bench_graph.py --case cells (about 12 candidates per receiver) at N = 20,000
+    (g = 17 cells per axis): against method="brute" on the same device, which the tests above and
+    tests/test_gpu_neighbor.py pin to numpy at the small sizes. Built twice: the order in which the atomics
+    filled the cells must not show."""
+    N = 20000
+    side = 10.0 * (N / 1000.0) ** (1.0 / 3.0)
+    x = (np.random.RandomState(7).rand(N, 3) * side).astype(np.float32)
+    a, b = _both(x, 1, N, 16, 1.5)
+    _same_graph(a, b)
+    c = graph.neighbor_graph(_dev(x), 1, N, 16, 1.5, method="cells")
+    _same_graph(b, c)
+    assert graph.neighbor_method("auto", 1.5, N) == "cells"          # past the measured crossover
+    _same_graph(b, graph.neighbor_graph(_dev(x), 1, N, 16, 1.5, method="auto"))
+    deg = np.diff(b.row_ptr.cpu().numpy())
+    assert 11.0 < deg.mean() < 14.0 and deg.max() == 16 and deg.min() < 8    # (12.6 on a sample of the reference)
+
+
+def test_cells_repeat_bitwise_on_a_mixed_batch():
+    x = _dev((np.random.RandomState(3).rand(sum(SIZES), 3) * 6).astype(np.float32))
+    runs = [graph.neighbor_graph_ragged(x, SIZES, 16, 1.0, method="cells", by_sender=True) for _ in range(2)]
+    _same_graph(runs[0], runs[1], sender=True)
+    assert int(runs[0].n_edges.item()) > 0
+
+
+# ---- 5. rollouts and models on a cells-built graph ------------------------------------------------------------
+@pytest.fixture(scope="module")
+def egno_fx():
+    return load_golden("egno_fwd")
+
+
+@pytest.fixture(scope="module")
+def segno_fx():
+    return load_golden("segno_fwd")
+
+
+def _egno(fx, T=10, mode="any"):
+    m = pkg.EGNO(n_layers=4, in_node_nf=2, in_edge_nf=2, hidden_nf=64, with_v=True, num_modes=2, num_timesteps=T,
+                 time_emb_dim=32, device=DEV, graph=mode)
+    m.load_state_dict({k: torch.tensor(v) for k, v in params_of(fx).items()})
+    return m.eval() if mode == "any" else m.train()
+
+
+def _segno(fx):
+    m = pkg.SEGNO(in_node_nf=1, in_edge_nf=2, hidden_nf=64, n_layers=8, recurrent=True, device=DEV, graph="any")
+    m.load_state_dict({k: torch.tensor(v) for k, v in params_of(fx).items()})
+    return m.eval()
+
+
+def _rollout_inputs(B, N, seed):
+    rs = np.random.RandomState(seed)
+    loc = (rs.randn(B, N, 3) * 1.5).astype(np.float32)
+    vel = (rs.randn(B, N, 3) * 0.3).astype(np.float32)
+    q = rs.choice([-1.0, 1.0], size=(B, N, 1)).astype(np.float32)
+    return _dev(loc), _dev(vel), _dev(q)
+
+
+R_CUT = 2.0
+
+
+@pytest.mark.parametrize("sizes", [None, [20, 37]])
+def test_rollouts_are_the_same_by_either_search(egno_fx, segno_fx, sizes):
+    B, N, k = 2, 37, 6
+    loc, vel, q = _rollout_inputs(B, N, 3)
+    me, ms = _egno(egno_fx), _segno(segno_fx)
+    if sizes is None:
+        ea = (loc, vel, q, N, B, 2)
+        sa = (loc.reshape(-1, 3), vel.reshape(-1, 3), q, B, 2, [3, 4])
+        kw = {}
+    else:
+        n = sum(sizes)
+        f = lambda t: t.reshape(B * N, -1)[:n].contiguous()   # noqa: E731
+        ea = (f(loc), f(vel), f(q), None, None, 2)
+        sa = (f(loc), f(vel), f(q), None, 2, [3, 4])
+        kw = dict(sizes=graph.RaggedBatch(sizes, loc.device))
+    out = {}
+    for meth in ("brute", "cells"):
+        pe, en, _, ge = harness.egno_rollout_graph(me, *ea, k=k, r_cut=R_CUT, energy_dataset="charged",
+                                                   return_graphs=True, neighbor_method=meth, **kw)
+        ps, es, gs = harness.segno_rollout_graph(ms, *sa, k=k, r_cut=R_CUT, energy_dataset="charged",
+                                                 return_graphs=True, neighbor_method=meth, **kw)
+        out[meth] = (pe, en, ps, es, ge + gs)
+    torch.cuda.synchronize()
+    a, b = out["brute"], out["cells"]
+    for u, v in zip(a[:4], b[:4]):
+        assert torch.equal(u, v)                         # (equal: no NaN on either side)
+    for ga, gb in zip(a[4], b[4]):
+        _same_graph(ga, gb)
+    E = int(a[4][0].n_edges.item())
+    assert 0 < E < a[4][0].capacity                      # the cut-off bites
+
+
+def test_training_rollout_is_the_same_by_either_search(egno_fx):
+    B, N, k = 2, 37, 6
+    loc, vel, q = _rollout_inputs(B, N, 3)
+    m = _egno(egno_fx, mode="trainable")
+    res = {}
+    for meth in ("brute", "cells"):
+        m.zero_grad(set_to_none=True)
+        preds = harness.egno_rollout_train_graph(m, loc, vel, q, N, B, 2, k=k, r_cut=R_CUT, neighbor_method=meth)
+        preds.square().mean().backward()
+        res[meth] = (preds.detach().clone(), [p.grad.clone() for p in m.parameters() if p.grad is not None])
+    torch.cuda.synchronize()
+    assert torch.equal(res["brute"][0], res["cells"][0]) and torch.isfinite(res["cells"][0]).all()
+    assert len(res["brute"][1]) == len(res["cells"][1]) > 0
+    for ga, gb in zip(res["brute"][1], res["cells"][1]):
+        assert torch.equal(ga, gb)
+
+
+def test_a_cells_rollout_does_not_synchronise(egno_fx):
+    B, N, k = 2, 37, 6
+    loc, vel, q = _rollout_inputs(B, N, 53)
+    me = _egno(egno_fx)
+
+    def run():
+        harness.egno_rollout_graph(me, loc, vel, q, N, B, 2, k=k, r_cut=R_CUT, energy_dataset="charged",
+                                   neighbor_method="cells")
+
+    run()                                   # warm-up: weight packing, allocator
+    torch.cuda.synchronize()
+    probe = torch.ones(1, device=DEV)
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        try:
+            probe.item()
+            raises = False
+        except RuntimeError:
+            raises = True
+        if raises:
+            run()
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    torch.cuda.synchronize()
+    if not raises:
+        pytest.skip("torch.cuda.set_sync_debug_mode('error') does not raise on .item() in this torch build")
+
+
+def test_a_model_on_a_cells_built_graph_equals_the_brute_built_one(egno_fx):
+    B, N, k = 2, 37, 6
+    n = B * N
+    rs = np.random.RandomState(21)
+    x = _dev(_points(n, 11))
+    v = _dev((rs.randn(n, 3) * 0.3).astype(np.float32))
+    h = _dev(rs.randn(n, 2).astype(np.float32))
+    lm = x.reshape(B, N, 3).mean(1, keepdim=True).expand(B, N, 3).reshape(n, 3).contiguous()
+    a = graph.neighbor_graph(x, B, N, k, 1.5, method="brute")
+    b = graph.neighbor_graph(x, B, N, k, 1.5, method="cells")
+    assert isinstance(b, graph.NeighborGraph) and 0 < int(b.n_edges.item()) < b.capacity
+    ef = _dev(rs.randn(b.capacity, 2).astype(np.float32))
+    m = _egno(egno_fx)
+    with torch.no_grad():
+        ya, yb = m(x, h, a, ef, v=v, loc_mean=lm), m(x, h, b, ef, v=v, loc_mean=lm)
+    torch.cuda.synchronize()
+    for u, w in zip(ya, yb):
+        assert torch.isfinite(u).all() and torch.equal(u, w)

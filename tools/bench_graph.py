@@ -1,7 +1,7 @@
 """Timings of the general-graph path (EGNO graph="any", csrc/nonode_graph.hip) on the GPU. One JSON
 line per case on stdout (DESIGN.md section 3.7 quotes them; raw lines under profiles/graph/).
 
-python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|ragged_rollout|knn_rollout_train|segno_train|all] [--reps 7] [--iters 20] [--arm both|ours]
+python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|ragged_rollout|knn_rollout_train|segno_train|cells|cells_rollout|all] [--reps 7] [--iters 20] [--arm both|ours]
 
   price  the C2 graph (B = 512, N = 20, T = 10: 5120 fully connected graphs per layer launch) through
          the fused layer entry (nonode_egnn_layer) and, passed as an edge list, through the general one
@@ -40,6 +40,12 @@ python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|ragged_rollo
          SEGNO(graph="any", trainable=True).train() (MSE on x; every live parameter's gradient) against fp32 autograd
          of oracle/torch_ref.segno_forward_step (dense_mean=False) on the graph's list on the same device, alternated
          likewise. --arm ours runs the HIP arm alone.
+  cells  the neighbour-graph builder alone under a cut-off, the brute-force search (method="brute") against the
+         cell list (method="cells"), alternated likewise: uniform points in a cube at about 12 candidates per
+         receiver (r_cut = 1.5, side 10 (N / 1000)^(1/3)), k = 16, one graph of 1,000 .. 100,000 nodes and
+         8 x 1000; one line per shape, with whether the two gave the same arrays.
+  cells_rollout  knn_rollout under that cut-off at 8 x 1000 and 1 x 20,000, the graph rebuilt every segment by
+         either search (harness.egno_rollout_graph(neighbor_method=...)), alternated likewise.
 Times are device events around `iters` back-to-back calls after a warm-up; each case reports the median
 over the reps and the spread (min, max) beside it.
 """
@@ -501,10 +507,78 @@ def case_segno_train(args):
     return res
 
 
+def uniform_cube(B, N, seed):
+    """B x N uniform points in a cube whose side grows with N^(1/3) from 10 at N = 1000: with r_cut = 1.5 about
+    12 candidates per receiver at every size (11.5 at N = 1000; fewer near the faces)."""
+    g = torch.Generator().manual_seed(seed)
+    side = 10.0 * (N / 1000.0) ** (1.0 / 3.0)
+    return (torch.rand(B * N, 3, generator=g) * side).to(DEV), side
+
+
+CELLS_SHAPES = ((1, 1000), (1, 4000), (1, 10000), (1, 20000), (1, 50000), (1, 100000), (8, 1000))
+CELLS_K, CELLS_RCUT = 16, 1.5
+
+
+def case_cells(args):
+    """The builder alone (graph.neighbor_graph: every launch of one build and its output allocations), method=
+    "brute" against method="cells", alternated; one line per shape."""
+    out = []
+    for B, N in CELLS_SHAPES:
+        x, side = uniform_cube(B, N, 7)
+        arms = {m: (lambda m=m: graph.neighbor_graph(x, B, N, CELLS_K, CELLS_RCUT, method=m)) for m in ("brute", "cells")}
+        a, b = arms["brute"](), arms["cells"]()
+        same = all(torch.equal(getattr(a, n), getattr(b, n)) for n in ("row_ptr", "col", "rows", "eid"))
+        E = int(a.n_edges.item())
+        iters = args.iters if N <= 20000 else max(args.iters // 4, 3)
+        t = alternate(arms, args.reps, iters)
+        br, ce = stats(t["brute"]), stats(t["cells"])
+        out.append({"case": "cells", "shape": {"graphs": B, "nodes_per_graph": N, "k": CELLS_K, "r_cut": CELLS_RCUT,
+                                               "cube_side": side, "cells_per_axis": max(g for g in range(1, 700) if 4 * g ** 3 <= max(N, 4))},
+                    "iters_per_rep": iters, "mean_degree": E / (B * N), "cells_bitwise_equal_to_brute": same,
+                    "brute": br, "cells": ce, "brute_per_rep_ms": t["brute"], "cells_per_rep_ms": t["cells"],
+                    "speedup": br["median_ms"] / ce["median_ms"],
+                    "cells_faster_on_every_alternation": all(c < b_ for b_, c in zip(t["brute"], t["cells"]))})
+    return out
+
+
+def case_cells_rollout(args):
+    """knn_rollout with a cut-off (uniform cube, r_cut = 1.5, k = 16, traj_len = 4, the damped heads), the graph
+    rebuilt every segment by either search: harness.egno_rollout_graph(neighbor_method=...), alternated."""
+    T, SEG, DAMP = 10, 4, 0.01
+    out = []
+    for B, N in ((8, 1000), (1, 20000)):
+        x, side = uniform_cube(B, N, 9)
+        loc = x.reshape(B, N, 3)
+        _, vel, q = synthetic(B, N, 2)
+        t_out = torch.arange(1, T * SEG + 1, device=DEV).repeat(B, 1)
+        m = model(T, graph="any")
+        with torch.no_grad():
+            for layer in m.layers:
+                for head in (layer.coord_net, layer.node_v_net):
+                    head.mlp[2].weight.mul_(DAMP)
+                    head.mlp[2].bias.mul_(DAMP)
+        arms = {meth: (lambda meth=meth: harness.egno_rollout_graph(
+            m, loc, vel, q, N, B, SEG, k=CELLS_K, r_cut=CELLS_RCUT, timesteps_out=t_out, neighbor_method=meth)[0])
+            for meth in ("brute", "cells")}
+        a, b = arms["brute"](), arms["cells"]()
+        same = bool(torch.equal(a, b))
+        iters = max(args.iters // 4, 3)
+        t = alternate(arms, args.reps, iters)
+        br, ce = stats(t["brute"]), stats(t["cells"])
+        out.append({"case": "cells_rollout", "shape": {"graphs": B, "nodes_per_graph": N, "k": CELLS_K, "r_cut": CELLS_RCUT,
+                                                       "cube_side": side, "T": T, "layers": 4, "traj_len": SEG},
+                    "iters_per_rep": iters, "model": f"untrained, last layers of coord_net and node_v_net scaled by {DAMP}",
+                    "positions_bitwise_equal": same, "last_frame_finite": bool(torch.isfinite(a[-1]).all()),
+                    "brute": br, "cells": ce, "brute_per_rep_ms": t["brute"], "cells_per_rep_ms": t["cells"],
+                    "speedup": br["median_ms"] / ce["median_ms"],
+                    "cells_faster_on_every_alternation": all(c < b_ for b_, c in zip(t["brute"], t["cells"]))})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="all", choices=["price", "knn", "knn_train", "knn_rollout", "ragged_rollout", "knn_rollout_train", "segno_train",
-                                                    "all"])
+                                                    "cells", "cells_rollout", "all"])
     ap.add_argument("--arm", default="both", choices=["both", "ours"], help="knn_train, knn_rollout, knn_rollout_train, segno_train: the HIP arm alone")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
@@ -514,11 +588,12 @@ def main():
     for name, fn in (("price", case_price), ("knn", case_knn), ("knn_train", case_knn_train),
                      ("knn_rollout", case_knn_rollout), ("ragged_rollout", case_ragged_rollout),
                      ("knn_rollout_train", case_knn_rollout_train),
-                     ("segno_train", case_segno_train)):
+                     ("segno_train", case_segno_train), ("cells", case_cells), ("cells_rollout", case_cells_rollout)):
         if args.case in (name, "all"):
             res = fn(args)
-            res["device"] = torch.cuda.get_device_name(0)
-            print(json.dumps(res), flush=True)
+            for line in res if isinstance(res, list) else [res]:
+                line["device"] = torch.cuda.get_device_name(0)
+                print(json.dumps(line), flush=True)
     graph.sync_checks()
 
 
