@@ -786,6 +786,40 @@ int nonode_debug_neighbor_cells(int G, int n_total, int n_max, float r2_max, con
                                 float* rr_out, int* grid, float* box, int* cell, int* range);
 
 /*
+ * The same graph for ANY r2_max > 0 (+inf: the pure k-NN graph) from the same cell list, the radius found per
+ * receiver instead of being given: for every input, row_ptr, col, rows, eid and the (-1, -1, p) tail are bitwise
+ * what nonode_neighbor_graph_ragged (nonode_neighbor_graph) writes. Arguments, refusals (all but the finiteness
+ * of r2_max) and workspace as nonode_neighbor_graph_cells. The grid has cell width extent / g per axis. One wave
+ * per receiver: (1) the box of cells [c - s, c + s] around its own cell c, s grown from 1 until the box holds
+ * kk = min(k, N_g - 1) other nodes (from the cell table alone) or covers the grid, goes through the
+ * keep-the-k-smallest code; D = the kk-th smallest d2 found, or r2_max if fewer were found and it is finite;
+ * (2) the cut-off search with r2_max := D, a radius rr with rr*rr > D in f32 computed on the device, of which only
+ * the cells outside the first box are still walked. Exact because the kk smallest keys all have d2 <= D (D is the
+ * kk-th smallest over a subset) and every node with d2 <= D has its cell in the second box (the covering
+ * argument of nonode_neighbor_graph_cells, csrc/nonode_cells.h). A receiver walks its whole graph instead (the
+ * search of nonode_neighbor_graph on the sorted copy) when it has a non-finite coordinate, when kk = N_g - 1,
+ * when D is not finite (under r2_max = +inf a node at +-inf is a candidate with d2 = inf, a NaN never is) or
+ * when no rr is found. Bitwise reproducible, asynchronous, nothing sized from device data.
+ */
+size_t nonode_neighbor_graph_knn_cells_workspace_bytes(int G, int n_total, int n_max, int k);
+int nonode_neighbor_graph_knn_cells(int G, int n_total, int n_max, int k, long long cap, float r2_max,
+                                    const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
+                                    int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Diagnostic, HOST arrays and no device: nonode_neighbor_graph_knn_cells receiver by receiver, through the
+ * functions its kernel runs (the grid, the binning, the boxes, the radius, the distance and the keys), sequential
+ * where the kernel is a wave. graph_ptr [G + 1] (NULL: G graphs of n_max rows), x [n_total][3]; k in [1, 64],
+ * r2_max > 0 (+inf allowed). Outputs (each may be NULL), per receiver r: nbr [n_total][min(k, n_max - 1)] the kept
+ * senders (global rows, ascending; -1 past the degree); deg [n_total]; d_out [n_total] the bound D (-1: phase 1
+ * did not run); stats [n_total][16] = {the final half-width s of the first box (0: not run), its lowest cell per
+ * axis [3], its highest [3], the second box likewise [3] [3] (-1: none), the number of distances evaluated, 1 if
+ * the receiver walked its whole graph, the cells per axis g}. Returns NONODE_OK or NONODE_EINVAL.
+ */
+int nonode_debug_neighbor_knn_cells(int G, int n_total, int n_max, int k, float r2_max, const int* graph_ptr,
+                                    const float* x, int* nbr, int* deg, int* stats, float* d_out);
+
+/*
  * The same graph as a CSR by sender, which the reverse pass of the graph layer
  * (nonode_egnn_layer_graph_bwd) walks: what training on a graph rebuilt every step needs, made on the
  * device from the padded list and its device-side count (nonode_graph_build cannot take a list with a

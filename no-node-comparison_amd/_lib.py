@@ -48,6 +48,8 @@ SYMBOLS = (
     "nonode_neighbor_graph_ragged_workspace_bytes", "nonode_neighbor_graph_ragged", "nonode_prepare_nodes_ragged",
     "nonode_prepare_inputs_bwd_ragged", "nonode_energy_ragged",
     "nonode_neighbor_graph_cells_workspace_bytes", "nonode_neighbor_graph_cells", "nonode_debug_neighbor_cells",
+    "nonode_neighbor_graph_knn_cells_workspace_bytes", "nonode_neighbor_graph_knn_cells",
+    "nonode_debug_neighbor_knn_cells",
 )
 
 VARIANT_EGNO = 0
@@ -278,6 +280,10 @@ def lib():
     L.nonode_neighbor_graph_cells_workspace_bytes.restype = _sz
     L.nonode_neighbor_graph_cells.argtypes = L.nonode_neighbor_graph_ragged.argtypes
     L.nonode_debug_neighbor_cells.argtypes = [_i, _i, _i, _f] + [_vp] * 7
+    L.nonode_neighbor_graph_knn_cells_workspace_bytes.argtypes = [_i] * 4
+    L.nonode_neighbor_graph_knn_cells_workspace_bytes.restype = _sz
+    L.nonode_neighbor_graph_knn_cells.argtypes = L.nonode_neighbor_graph_ragged.argtypes
+    L.nonode_debug_neighbor_knn_cells.argtypes = [_i, _i, _i, _i, _f] + [_vp] * 6
     L.nonode_prepare_nodes_ragged.argtypes = [_i] * 3 + [_vp] * 10
     L.nonode_prepare_inputs_bwd_ragged.argtypes = [_i] * 3 + [_vp] * 8
     L.nonode_energy_ragged.argtypes = [_i] * 4 + [_vp] * 6

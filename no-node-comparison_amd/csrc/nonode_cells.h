@@ -1,7 +1,8 @@
-// nonode_cells.h — the uniform grid of the cut-off neighbour search (nonode_neighbor.hip): the grid rule, the
-// binning function and a receiver's search box, written once as __host__ __device__ functions that the
-// kernels and the host entry nonode_debug_neighbor_cells share (as seg_walk is shared with
-// nonode_debug_edge_walk), so what a test checks on the host is what the device runs.
+// nonode_cells.h — the uniform grid of the cut-off and k-NN neighbour searches (nonode_neighbor.hip): the grid rule,
+// the binning function, a receiver's search boxes and the radius of the k-NN search, written once as
+// __host__ __device__ functions that the kernels and the host entries nonode_debug_neighbor_cells /
+// nonode_debug_neighbor_knn_cells share (as seg_walk is shared with nonode_debug_edge_walk), so what a test
+// checks on the host is what the device runs.
 //
 // Why the search misses no candidate. Everything is per axis, with fl() the
 // rounding of one f32 operation, and rests on rounded operations being monotone, not on a margin:
@@ -20,6 +21,29 @@
 // A node with a non-finite coordinate has no cell: under a finite r2_max it is nobody's candidate and has
 // none (inf - x = inf squares to inf, inf - inf is NaN). It stays out of the bounding box and goes to a
 // trailing bucket of the sort, so the sorted order still holds every node exactly once.
+//
+// The k-NN search on the same grid (neighbor_select_knn_cells_kernel): the radius is
+// found per receiver instead of being given. The grid is built with rr = 0, so the width is extent / g alone.
+//   Phase 1: the shell box [c - s, c + s] (clamped) around the receiver's own cell c, s grown from 1 until the
+//     box holds kk other nodes (cell_start differences) or covers the grid, is fed to the keep-the-k-smallest
+//     body. D = the kk-th smallest d2 found; fewer than kk found: D = r2_max if that is finite.
+//   Phase 2: the cut-off search above with r2_max := D, i.e. cell_box(x_i, rr) with fl(rr rr) > D (knn_rr), of
+//     which only the cells outside the shell box are still to be walked (box_run_outside): every node is in
+//     one cell, so no key is fed twice.
+//   Exact, because: (1) D is the kk-th smallest d2 over a SUBSET of the candidates, so the kk-th smallest over
+//     all of them is <= D and every one of the true kk smallest keys has d2 <= D (ties at D included), or, with
+//     D = r2_max, every candidate has; (2) by the covering argument above, which holds for d2 <= r2 with any
+//     r2 and its rr, every j with d2 <= D has its cell in cell_box(x_i, rr); (3) so the keys fed, shell box and
+//     box 2 together, are a set of candidates that contains the true kk smallest, and the kk smallest of that
+//     set are the kk smallest of all. What the shell box feeds beyond box 2 are real candidates and do no harm.
+//   A zero extent on an axis gives w = 0 and inv_w = +inf there (also a width that underflows, and the NaN
+//     width of a graph without a finite node): cell_of is then 0 for x <= lo (-inf, and the NaN of 0 inf) and
+//     g - 1 for x > lo (+inf): still one monotone function of x, which is all (2) uses, so the behaviour is
+//     kept; with zero extent every node has x = lo and lands in cell 0.
+//   The receiver walks its whole graph instead (the brute-force search on the sorted copy, the non-finite
+//     bucket included) when it has a non-finite coordinate, when kk = N_g - 1 (every other node is wanted), when
+//     D is not finite (fewer than kk finite nodes under r2_max = +inf, where a node at +-inf is a candidate with
+//     d2 = inf, or a d2 that overflowed), or when knn_rr finds no radius.
 #pragma once
 
 #pragma clang fp contract(off)
@@ -106,6 +130,70 @@ inline float cell_rr(float r2_max) {
   float rr = sqrtf(r2_max) * (1.0f + 0x1p-20f);
   while (!(rr * rr > r2_max)) rr *= 1.0f + 0x1p-10f;
   return rr;
+}
+
+// ---- the k-NN search on the grid (header comment) ----
+
+// the shell box of half-width s around cell c, clamped to the grid
+__host__ __device__ __forceinline__ CellBox shell_box(int c0, int c1, int c2, int s, int g) {
+  const int c[3] = {c0, c1, c2};
+  CellBox b;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    b.lo[a] = c[a] - s > 0 ? c[a] - s : 0;
+    b.hi[a] = c[a] + s < g - 1 ? c[a] + s : g - 1;
+  }
+  return b;
+}
+__host__ __device__ __forceinline__ bool box_covers_grid(const CellBox& b, int g) {
+  return b.lo[0] <= 0 && b.lo[1] <= 0 && b.lo[2] <= 0 && b.hi[0] >= g - 1 && b.hi[1] >= g - 1 && b.hi[2] >= g - 1;
+}
+__host__ __device__ __forceinline__ bool box_inside(const CellBox& b, const CellBox& in) {
+  return b.lo[0] >= in.lo[0] && b.lo[1] >= in.lo[1] && b.lo[2] >= in.lo[2] && b.hi[0] <= in.hi[0] &&
+         b.hi[1] <= in.hi[1] && b.hi[2] <= in.hi[2];
+}
+
+// Cells c0 .. c1 (z fastest) of a graph's grid: one contiguous run of the sorted order; c0 > c1: none.
+struct CellSeg {
+  int c0, c1;
+};
+__host__ __device__ __forceinline__ int box_runs(const CellBox& b) {
+  return (b.hi[0] - b.lo[0] + 1) * (b.hi[1] - b.lo[1] + 1);
+}
+// run u of box b, u < box_runs(b): the cells (cx, cy, z_lo .. z_hi), (cx, cy) = (lo0 + u / ny, lo1 + u % ny)
+__host__ __device__ __forceinline__ CellSeg box_run(const CellBox& b, int u, int g) {
+  const int ny = b.hi[1] - b.lo[1] + 1;
+  const int c = ((b.lo[0] + u / ny) * g + b.lo[1] + u % ny) * g;
+  return CellSeg{c + b.lo[2], c + b.hi[2]};
+}
+// half h (0: below, 1: above) of run u of box b, without the cells of box `in`: a run whose (cx, cy) is outside
+// in's is whole in its lower half; one inside leaves z_lo .. in.lo2 - 1 below and in.hi2 + 1 .. z_hi above
+__host__ __device__ __forceinline__ CellSeg box_run_outside(const CellBox& b, const CellBox& in, int u, int h, int g) {
+  const int ny = b.hi[1] - b.lo[1] + 1;
+  const int cx = b.lo[0] + u / ny, cy = b.lo[1] + u % ny;
+  const int c = (cx * g + cy) * g;
+  const bool over = cx >= in.lo[0] && cx <= in.hi[0] && cy >= in.lo[1] && cy <= in.hi[1];
+  if (!over) return h == 0 ? CellSeg{c + b.lo[2], c + b.hi[2]} : CellSeg{1, 0};
+  if (h == 0) return CellSeg{c + b.lo[2], c + (b.hi[2] < in.lo[2] - 1 ? b.hi[2] : in.lo[2] - 1)};
+  return CellSeg{c + (b.lo[2] > in.hi[2] + 1 ? b.lo[2] : in.hi[2] + 1), c + b.hi[2]};
+}
+
+// The search radius of a finite D >= 0, found per receiver on the device: a float rr with fl(rr rr) > D, which
+// is all the covering argument asks (cell_rr's property). From just above the square root, and from 2^-74 (the
+// smallest power of two whose square is not zero) where D is zero or tiny; raised by 2^-10 a few times (the
+// product's rounding is coarse where it is subnormal), then by a quarter a time, 64 steps at the most; a
+// product that overflows is +inf > D. False: none found (the receiver walks its whole graph).
+__host__ __device__ __forceinline__ bool knn_rr(float D, float* rr_out) {
+  float rr = sqrtf(D) * (1.0f + 0x1p-20f);
+  if (!(rr >= 0x1p-74f)) rr = 0x1p-74f;
+  for (int it = 0; it < 64; ++it) {
+    if (rr * rr > D) {
+      *rr_out = rr;
+      return true;
+    }
+    rr *= it < 4 ? 1.0f + 0x1p-10f : 1.25f;
+  }
+  return false;
 }
 
 }  // namespace

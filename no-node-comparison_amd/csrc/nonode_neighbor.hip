@@ -18,6 +18,9 @@
 //                           a cell list (nonode_neighbor_graph_cells): each graph's nodes binned into a
 //                           uniform grid and sorted by cell, one wave per receiver over the cells its cut-off
 //                           box touches, the candidates through the same keep-the-k-smallest body
+//   neighbor_select_knn_cells_kernel  the same rows for ANY r2_max (+inf: the pure k-NN graph) from the same cell
+//                           list (nonode_neighbor_graph_knn_cells): a box of cells that holds k other nodes bounds
+//                           the k-th distance, and the cut-off search with that bound finds the rest
 //   (scan)                  row_ptr = exclusive prefix sum of the degrees (nonode_graph.hip's
 //                           one-workgroup scan)
 //   neighbor_compact_kernel fixed-pitch rows -> CSR (col, rows, eid), and the -1 tail
@@ -32,6 +35,8 @@
 // sum of the sizes) and graph_of [n_total] (the *_ragged entries): the same kernels, which take a graph's
 // bounds from graph_rows (nonode_common.h) where the equal-size call divides.
 #include "nonode_common.h"
+
+#include <algorithm>
 
 #pragma clang fp contract(off)
 
@@ -71,7 +76,7 @@ __device__ __forceinline__ u64 bitonic_sort(u64 v, int lane) {
 }
 
 // d2 = ((d0 d0) + (d1 d1)) + (d2 d2), every operation rounded to f32 on its own
-__device__ __forceinline__ float dist2(float a0, float a1, float a2, float b0, float b1, float b2) {
+__host__ __device__ __forceinline__ float dist2(float a0, float a1, float a2, float b0, float b1, float b2) {
   const float d0 = a0 - b0, d1 = a1 - b1, d2 = a2 - b2;
   return ((d0 * d0) + (d1 * d1)) + (d2 * d2);
 }
@@ -302,6 +307,136 @@ __global__ __launch_bounds__(256) void neighbor_select_cells_kernel(
   topk_write(best, kk, lane, r, g0, pitch, tmp, deg);
 }
 
+// ---- the k-NN search on the cell list (any r2_max, +inf included): the radius is found per receiver ----
+// nonode_cells.h has the two phases, why they are exact and when a receiver walks its whole graph instead.
+// Same grid kernels as above (built with rr = 0: the width is extent / g), same dist2, same keys, same topk.
+
+// nseg segments of the sorted order through topk_chunk, segment u = sorted[p .. e) from seg(u, p, e): the lanes
+// take several segments at once, as neighbor_select_cells_kernel's do (groups of 16, 32 or all 64 lanes).
+template <class Seg>
+__device__ __forceinline__ void walk_segments(u64& best, int nseg, Seg seg, int n_total, int kk, int lane, int i,
+                                              int g0, float r2_max, float xi0, float xi1, float xi2,
+                                              const f4* __restrict__ sorted) {
+  const int sh = nseg >= 4 ? 4 : (nseg >= 2 ? 5 : 6);   // log2 of the lanes per segment
+  const int grp = lane >> sh, sub = lane & ((1 << sh) - 1);
+  for (int u0 = 0; u0 < nseg; u0 += 64 >> sh) {
+    const int u = u0 + grp;
+    int p = 0, e = 0;
+    if (u < nseg) seg(u, p, e);
+    p += sub;
+    e = imin(e, n_total);
+    while (__any(p < e)) {
+      u64 key = KEY_NONE;
+      if (p >= 0 && p < e) {
+        const f4 o = sorted[p];
+        const int j = __float_as_int(o[3]) - g0;
+        const float d2 = dist2(xi0, xi1, xi2, o[0], o[1], o[2]);
+        // d2 >= +0 here (a NaN fails the compare), so its bits order as an unsigned integer
+        if (j != i && d2 <= r2_max) key = ((u64)__float_as_uint(d2) << 32) | (unsigned)j;
+      }
+      topk_chunk(best, key, kk, lane);
+      p += 1 << sh;
+    }
+  }
+}
+__device__ __forceinline__ CellBox uniform_box(const CellBox& b) {   // the same in every lane: scalar registers
+  CellBox u;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    u.lo[a] = __builtin_amdgcn_readfirstlane(b.lo[a]);
+    u.hi[a] = __builtin_amdgcn_readfirstlane(b.hi[a]);
+  }
+  return u;
+}
+
+// One wave per receiver, in sorted order. Every branch below is wave-uniform (all lanes hold the same receiver).
+// (NONODE_KNN_REWALK=1 builds drop phase 1's keys and walk the whole of box 2 where it leaves the shell box, in
+// place of the cells outside it alone: the A/B of DESIGN.md section 3.7.2.)
+#ifndef NONODE_KNN_REWALK
+#define NONODE_KNN_REWALK 0
+#endif
+__global__ __launch_bounds__(256) void neighbor_select_knn_cells_kernel(
+    int n_total, int n_each, int k, int pitch, float r2_max, int n_graphs, const int* __restrict__ graph_ptr,
+    const int* __restrict__ graph_of, const f4* __restrict__ sorted, const int* __restrict__ cell_start,
+    const unsigned* __restrict__ bb, int* __restrict__ tmp, int* __restrict__ deg) {
+  const int lane = threadIdx.x & 63;
+  const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= n_total) return;   // (wave-uniform)
+  const f4 me = sorted[s];
+  const int r = __builtin_amdgcn_readfirstlane(__float_as_int(me[3]));
+  if (r < 0 || r >= n_total) return;   // (the fill wrote every slot: never)
+  const NodeGraph ng = node_graph(r, n_total, n_each, n_graphs, graph_ptr, graph_of);
+  const int g0 = __builtin_amdgcn_readfirstlane(ng.g0), N = __builtin_amdgcn_readfirstlane(ng.n);
+  const int gi = __builtin_amdgcn_readfirstlane(ng.gi);
+  const int kk = imin(imin(k, N - 1), pitch), i = r - g0;
+  if (kk <= 0) {   // a graph of one node: no pair
+    if (lane == 0) deg[r] = 0;
+    return;
+  }
+  const float xi0 = me[0], xi1 = me[1], xi2 = me[2];
+  const int tab = g0 + gi, last = n_total + n_graphs - 1;
+  u64 best = KEY_NONE;
+  bool whole = !cell_finite(xi0, xi1, xi2) || kk >= N - 1;
+  if (!whole) {
+    const CellGrid cg = cell_grid(bb + (size_t)gi * 6, N, 0.f);
+    const int g = cg.g;
+    const int c0 = __builtin_amdgcn_readfirstlane(cell_of(xi0, cg.lo[0], cg.inv_w[0], g));
+    const int c1 = __builtin_amdgcn_readfirstlane(cell_of(xi1, cg.lo[1], cg.inv_w[1], g));
+    const int c2 = __builtin_amdgcn_readfirstlane(cell_of(xi2, cg.lo[2], cg.inv_w[2], g));
+    // phase 1: the shell box, grown until it holds kk nodes beside the receiver (or is the grid; hw <= g)
+    CellBox b1;
+    for (int hw = 1;; ++hw) {
+      b1 = shell_box(c0, c1, c2, hw, g);
+      if (box_covers_grid(b1, g)) break;
+      int cnt = 0;
+      for (int u = lane; u < box_runs(b1); u += 64) {
+        const CellSeg sg = box_run(b1, u, g);
+        cnt += cell_start[imin(tab + sg.c1, last) + 1] - cell_start[imin(tab + sg.c0, last)];
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+      if (__builtin_amdgcn_readfirstlane(cnt) - 1 >= kk) break;
+    }
+    walk_segments(best, box_runs(b1), [&](int u, int& p, int& e) {
+      const CellSeg sg = box_run(b1, u, g);
+      p = cell_start[imin(tab + sg.c0, last)];
+      e = cell_start[imin(tab + sg.c1, last) + 1];
+    }, n_total, kk, lane, i, g0, r2_max, xi0, xi1, xi2, sorted);
+    // phase 2: what the cut-off search with r2 = D walks outside the shell box
+    const u64 kth = shfl64(best, kk - 1);
+    const float D = kth != KEY_NONE ? __uint_as_float((unsigned)(kth >> 32)) : r2_max;
+    float rr = 0.f;
+    if (!cell_finite(D) || !knn_rr(D, &rr)) {
+      whole = true;
+    } else {
+      const CellBox b2 = uniform_box(cell_box(cg, xi0, xi1, xi2, rr));
+      if (!box_inside(b2, b1)) {
+#if NONODE_KNN_REWALK
+        best = KEY_NONE;
+        walk_segments(best, box_runs(b2), [&](int u, int& p, int& e) {
+          const CellSeg sg = box_run(b2, u, g);
+          p = cell_start[imin(tab + sg.c0, last)];
+          e = cell_start[imin(tab + sg.c1, last) + 1];
+        }, n_total, kk, lane, i, g0, r2_max, xi0, xi1, xi2, sorted);
+#else
+        walk_segments(best, 2 * box_runs(b2), [&](int u, int& p, int& e) {
+          const CellSeg sg = box_run_outside(b2, b1, u >> 1, u & 1, g);
+          if (sg.c0 > sg.c1) return;
+          p = cell_start[imin(tab + sg.c0, last)];
+          e = cell_start[imin(tab + sg.c1, last) + 1];
+        }, n_total, kk, lane, i, g0, r2_max, xi0, xi1, xi2, sorted);
+#endif
+      }
+    }
+  }
+  if (whole) {   // the brute-force search on the graph's run of the sorted order, its non-finite bucket included
+    best = KEY_NONE;
+    walk_segments(best, 1, [&](int, int& p, int& e) { p = g0; e = g0 + N; }, n_total, kk, lane, i, g0, r2_max, xi0,
+                  xi1, xi2, sorted);
+  }
+  topk_write(best, kk, lane, r, g0, pitch, tmp, deg);
+}
+
 // thread t = r pitch + l of the n_total pitch fixed-pitch slots: entry l of row r moves to row_ptr[r] + l;
 // position t of the outputs, when it is at or past the edge count, gets the tail's (-1, -1, t). The
 // outputs hold cap <= n_total pitch entries (equal sizes: cap = n_total pitch) and no store leaves [0, cap).
@@ -485,11 +620,12 @@ size_t cells_workspace_ints(int G, int n_total, int pitch) {
 
 // The cell-list builder's launches (finite r2_max): memset, bounding boxes, cell counts, scan, fill, the
 // search, then the brute-force builder's own scan and compaction. Every grid is a function of n_total and the
-// pitch; nothing is read back.
-int launch_neighbor_graph_cells(int n_total, int n_max, int k, long long cap, float r2_max, int n_graphs,
+// pitch; nothing is read back. knn: the k-NN search on the same list (any r2_max): the grid of rr = 0 and
+// neighbor_select_knn_cells_kernel in place of the cut-off's radius and search.
+int launch_neighbor_graph_cells(bool knn, int n_total, int n_max, int k, long long cap, float r2_max, int n_graphs,
                                 const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
                                 int* eid, int* rows, void* workspace, hipStream_t s) {
-  const char* who = "neighbor_graph_cells";
+  const char* who = knn ? "neighbor_graph_knn_cells" : "neighbor_graph_cells";
   const int pitch = k < n_max - 1 ? k : n_max - 1;
   if (pitch == 0) {   // graphs of one node: no pair at all
     if (hipMemsetAsync(row_ptr, 0, ((size_t)n_total + 1) * sizeof(int), s) != hipSuccess)
@@ -503,7 +639,7 @@ int launch_neighbor_graph_cells(int n_total, int n_max, int k, long long cap, fl
   unsigned* bb = (unsigned*)(bucket + n_total);
   int* cnt = (int*)(bb + 6 * (size_t)n_graphs);
   int* cell_start = cnt + n_total + n_graphs;
-  const float rr = cell_rr(r2_max);
+  const float rr = knn ? 0.f : cell_rr(r2_max);
   if (hipMemsetAsync(bb, 0, (6 * (size_t)n_graphs + (size_t)n_total + n_graphs) * sizeof(int), s) != hipSuccess)
     return fail(NONODE_ELAUNCH, "%s: memset", who);
   const dim3 per_node((n_total + 255) / 256), per_wave((n_total + 3) / 4);
@@ -515,9 +651,13 @@ int launch_neighbor_graph_cells(int n_total, int n_max, int k, long long cap, fl
   if (int rc = nonode_tu::graph_scan(n_total + n_graphs, cnt, cell_start, s)) return rc;
   hipLaunchKernelGGL(cell_fill_kernel, per_node, dim3(256), 0, s, n_total, x, bucket, cnt, sorted);
   if (int rc = check_launch("cell_fill_kernel")) return rc;
-  hipLaunchKernelGGL(neighbor_select_cells_kernel, per_wave, dim3(256), 0, s, n_total, n_max, k, pitch, r2_max, rr,
-                     n_graphs, graph_ptr, graph_of, sorted, cell_start, bb, tmp, deg);
-  if (int rc = check_launch("neighbor_select_cells_kernel")) return rc;
+  if (knn)
+    hipLaunchKernelGGL(neighbor_select_knn_cells_kernel, per_wave, dim3(256), 0, s, n_total, n_max, k, pitch, r2_max,
+                       n_graphs, graph_ptr, graph_of, sorted, cell_start, bb, tmp, deg);
+  else
+    hipLaunchKernelGGL(neighbor_select_cells_kernel, per_wave, dim3(256), 0, s, n_total, n_max, k, pitch, r2_max, rr,
+                       n_graphs, graph_ptr, graph_of, sorted, cell_start, bb, tmp, deg);
+  if (int rc = check_launch(knn ? "neighbor_select_knn_cells_kernel" : "neighbor_select_cells_kernel")) return rc;
   if (int rc = nonode_tu::graph_scan(n_total, deg, row_ptr, s)) return rc;
   const long long slots = (long long)n_total * pitch;
   hipLaunchKernelGGL(neighbor_compact_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, cap, n_total,
@@ -587,27 +727,48 @@ size_t nonode_neighbor_graph_cells_workspace_bytes(int G, int n_total, int n_max
   return cells_workspace_ints(G, n_total, k < n_max - 1 ? k : n_max - 1) * sizeof(int);
 }
 
+// the host checks and the launches of both searches on the cell list (knn: r2_max may be +inf)
+static int neighbor_graph_cells_entry(bool knn, int G, int n_total, int n_max, int k, long long cap, float r2_max,
+                                      const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
+                                      int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = knn ? "neighbor_graph_knn_cells" : "neighbor_graph_cells";
+  if (G < 1 || n_total < G || n_total >= (1 << 30) || n_max < 1 || n_max > n_total || k < 1 || k > 64 ||
+      !(r2_max > 0.f) || (!knn && !cell_finite(r2_max)) || cap < 0 || cap >= (1ll << 31) ||
+      cap > (long long)n_total * (k < n_max - 1 ? k : n_max - 1))
+    return fail(NONODE_EINVAL, "%s: G=%d n_total=%d n_max=%d k=%d cap=%lld r2_max=%g (k in [1, 64], r2_max > 0%s, "
+                "cap <= n_total min(k, n_max - 1))", who, G, n_total, n_max, k, cap, (double)r2_max,
+                knn ? "" : " and finite");
+  if ((graph_ptr == nullptr) != (graph_of == nullptr))
+    return fail(NONODE_EINVAL, "%s: graph_ptr and graph_of go together (both null: equal sizes)", who);
+  if (!graph_of && (long long)G * n_max != n_total)
+    return fail(NONODE_EINVAL, "%s: equal sizes need n_total = G n_max, got G=%d n_max=%d n_total=%d", who, G, n_max,
+                n_total);
+  if (!x || !row_ptr || !workspace || (cap > 0 && (!col || !eid || !rows)))
+    return fail(NONODE_EINVAL, "%s: null pointer", who);
+  if (((size_t)workspace & 15) != 0) return fail(NONODE_EINVAL, "%s: workspace not 16-byte aligned", who);
+  if (workspace_bytes < nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k))
+    return fail(NONODE_EINVAL, "%s: workspace %zu < %zu", who, workspace_bytes,
+                nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k));
+  return launch_neighbor_graph_cells(knn, n_total, n_max, k, cap, r2_max, G, graph_ptr, graph_of, x, row_ptr, col, eid,
+                                     rows, workspace, (hipStream_t)stream);
+}
+
 int nonode_neighbor_graph_cells(int G, int n_total, int n_max, int k, long long cap, float r2_max,
                                 const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
                                 int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream) {
-  if (G < 1 || n_total < G || n_total >= (1 << 30) || n_max < 1 || n_max > n_total || k < 1 || k > 64 ||
-      !(r2_max > 0.f) || !cell_finite(r2_max) || cap < 0 || cap >= (1ll << 31) ||
-      cap > (long long)n_total * (k < n_max - 1 ? k : n_max - 1))
-    return fail(NONODE_EINVAL, "neighbor_graph_cells: G=%d n_total=%d n_max=%d k=%d cap=%lld r2_max=%g (k in [1, 64], "
-                "r2_max > 0 and finite, cap <= n_total min(k, n_max - 1))", G, n_total, n_max, k, cap, (double)r2_max);
-  if ((graph_ptr == nullptr) != (graph_of == nullptr))
-    return fail(NONODE_EINVAL, "neighbor_graph_cells: graph_ptr and graph_of go together (both null: equal sizes)");
-  if (!graph_of && (long long)G * n_max != n_total)
-    return fail(NONODE_EINVAL, "neighbor_graph_cells: equal sizes need n_total = G n_max, got G=%d n_max=%d n_total=%d",
-                G, n_max, n_total);
-  if (!x || !row_ptr || !workspace || (cap > 0 && (!col || !eid || !rows)))
-    return fail(NONODE_EINVAL, "neighbor_graph_cells: null pointer");
-  if (((size_t)workspace & 15) != 0) return fail(NONODE_EINVAL, "neighbor_graph_cells: workspace not 16-byte aligned");
-  if (workspace_bytes < nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k))
-    return fail(NONODE_EINVAL, "neighbor_graph_cells: workspace %zu < %zu", workspace_bytes,
-                nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k));
-  return launch_neighbor_graph_cells(n_total, n_max, k, cap, r2_max, G, graph_ptr, graph_of, x, row_ptr, col, eid, rows,
-                                     workspace, (hipStream_t)stream);
+  return neighbor_graph_cells_entry(false, G, n_total, n_max, k, cap, r2_max, graph_ptr, graph_of, x, row_ptr, col, eid,
+                                    rows, workspace, workspace_bytes, stream);
+}
+
+size_t nonode_neighbor_graph_knn_cells_workspace_bytes(int G, int n_total, int n_max, int k) {
+  return nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k);   // the same list, the same rows
+}
+
+int nonode_neighbor_graph_knn_cells(int G, int n_total, int n_max, int k, long long cap, float r2_max,
+                                    const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
+                                    int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream) {
+  return neighbor_graph_cells_entry(true, G, n_total, n_max, k, cap, r2_max, graph_ptr, graph_of, x, row_ptr, col, eid,
+                                    rows, workspace, workspace_bytes, stream);
 }
 
 // Diagnostic (host arrays, no GPU): the grid, the binning and the search boxes of the cell-list search, from
@@ -656,6 +817,130 @@ int nonode_debug_neighbor_cells(int G, int n_total, int n_max, float r2_max, con
           range[(size_t)r * 6 + 3 + a] = bx.hi[a];
         }
       }
+    }
+  }
+  return NONODE_OK;
+}
+
+// Diagnostic (host arrays, no GPU): the k-NN search on the cell list, receiver by receiver, through the functions
+// neighbor_select_knn_cells_kernel runs (nonode_cells.h, dist2, the same keys): a sequential restatement of its
+// flow, with a sort where the wave keeps its 64 best.
+int nonode_debug_neighbor_knn_cells(int G, int n_total, int n_max, int k, float r2_max, const int* graph_ptr,
+                                    const float* x, int* nbr, int* deg, int* stats, float* d_out) {
+  if (G < 1 || n_total < G || n_max < 1 || n_max > n_total || k < 1 || k > 64 || !(r2_max > 0.f) || !x ||
+      (!graph_ptr && (long long)G * n_max != n_total))
+    return fail(NONODE_EINVAL, "debug_neighbor_knn_cells: G=%d n_total=%d n_max=%d k=%d r2_max=%g", G, n_total, n_max,
+                k, (double)r2_max);
+  const int pitch = k < n_max - 1 ? k : n_max - 1;
+  for (int gi = 0; gi < G; ++gi) {
+    int g0 = gi * n_max, n = n_max;
+    if (graph_ptr) {   // (graph_rows, on the host)
+      const int lo = imin(imax(graph_ptr[gi], 0), n_total), hi = imin(imax(graph_ptr[gi + 1], 0), n_total);
+      g0 = lo;
+      n = hi - lo;
+    }
+    const float* xg = x + (size_t)g0 * 3;
+    unsigned bb[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    for (int j = 0; j < n; ++j) {
+      if (!cell_finite(xg[j * 3], xg[j * 3 + 1], xg[j * 3 + 2])) continue;
+      for (int a = 0; a < 3; ++a) {
+        const unsigned key = cell_key(xg[j * 3 + a]);
+        if (~key > bb[a]) bb[a] = ~key;
+        if (key > bb[3 + a]) bb[3 + a] = key;
+      }
+    }
+    const CellGrid cg = cell_grid(bb, n, 0.f);
+    const int g = cg.g, nc = g * g * g;
+    // the graph's part of the sorted order: its nodes by cell (the order inside a cell does not matter), the
+    // non-finite ones in the trailing bucket nc; start = its part of cell_start
+    std::vector<int> bucket(n), start(nc + 2, 0), order(n);
+    for (int j = 0; j < n; ++j) {
+      const float* p = xg + (size_t)j * 3;
+      bucket[j] = nc;
+      if (cell_finite(p[0], p[1], p[2]))
+        bucket[j] = (cell_of(p[0], cg.lo[0], cg.inv_w[0], g) * g + cell_of(p[1], cg.lo[1], cg.inv_w[1], g)) * g +
+                    cell_of(p[2], cg.lo[2], cg.inv_w[2], g);
+      ++start[bucket[j] + 1];
+    }
+    for (int c = 0; c <= nc; ++c) start[c + 1] += start[c];
+    {
+      std::vector<int> cursor(start.begin(), start.end() - 1);
+      for (int j = 0; j < n; ++j) order[cursor[bucket[j]]++] = j;
+    }
+    const int kk = imin(imin(k, n - 1), pitch);
+    std::vector<u64> keys;
+    for (int i = 0; i < n; ++i) {
+      const int r = g0 + i;
+      const float xi0 = xg[i * 3], xi1 = xg[i * 3 + 1], xi2 = xg[i * 3 + 2];
+      int st[16] = {0, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0, 0, g};
+      float D = -1.f;
+      keys.clear();
+      auto feed = [&](int p, int e) {
+        for (; p < e; ++p) {
+          const int j = order[p];
+          const float d2 = dist2(xi0, xi1, xi2, xg[j * 3], xg[j * 3 + 1], xg[j * 3 + 2]);
+          ++st[13];
+          if (j != i && d2 <= r2_max) keys.push_back(((u64)__builtin_bit_cast(unsigned, d2) << 32) | (unsigned)j);
+        }
+      };
+      if (kk > 0) {
+        bool whole = !cell_finite(xi0, xi1, xi2) || kk >= n - 1;
+        if (!whole) {
+          const int c0 = cell_of(xi0, cg.lo[0], cg.inv_w[0], g), c1 = cell_of(xi1, cg.lo[1], cg.inv_w[1], g),
+                    c2 = cell_of(xi2, cg.lo[2], cg.inv_w[2], g);
+          CellBox b1;
+          int hw = 1;
+          for (;; ++hw) {
+            b1 = shell_box(c0, c1, c2, hw, g);
+            if (box_covers_grid(b1, g)) break;
+            int cnt = 0;
+            for (int u = 0; u < box_runs(b1); ++u) {
+              const CellSeg sg = box_run(b1, u, g);
+              cnt += start[sg.c1 + 1] - start[sg.c0];
+            }
+            if (cnt - 1 >= kk) break;
+          }
+          st[0] = hw;
+          for (int a = 0; a < 3; ++a) st[1 + a] = b1.lo[a], st[4 + a] = b1.hi[a];
+          for (int u = 0; u < box_runs(b1); ++u) {
+            const CellSeg sg = box_run(b1, u, g);
+            feed(start[sg.c0], start[sg.c1 + 1]);
+          }
+          D = r2_max;
+          if ((int)keys.size() >= kk) {
+            std::nth_element(keys.begin(), keys.begin() + (kk - 1), keys.end());
+            D = __builtin_bit_cast(float, (unsigned)(keys[kk - 1] >> 32));
+          }
+          float rr = 0.f;
+          if (!cell_finite(D) || !knn_rr(D, &rr)) {
+            whole = true;
+          } else {
+            const CellBox b2 = cell_box(cg, xi0, xi1, xi2, rr);
+            for (int a = 0; a < 3; ++a) st[7 + a] = b2.lo[a], st[10 + a] = b2.hi[a];
+            if (!box_inside(b2, b1))
+              for (int u = 0; u < 2 * box_runs(b2); ++u) {
+                const CellSeg sg = box_run_outside(b2, b1, u >> 1, u & 1, g);
+                if (sg.c0 <= sg.c1) feed(start[sg.c0], start[sg.c1 + 1]);
+              }
+          }
+        }
+        if (whole) {
+          keys.clear();
+          feed(0, n);
+        }
+        st[14] = whole ? 1 : 0;
+      }
+      std::sort(keys.begin(), keys.end());
+      const int d = imin((int)keys.size(), kk);
+      std::vector<int> row(d);
+      for (int l = 0; l < d; ++l) row[l] = (int)(unsigned)keys[l];
+      std::sort(row.begin(), row.end());
+      if (deg) deg[r] = d;
+      if (nbr)
+        for (int l = 0; l < pitch; ++l) nbr[(size_t)r * pitch + l] = l < d ? g0 + row[l] : -1;
+      if (stats)
+        for (int a = 0; a < 16; ++a) stats[(size_t)r * 16 + a] = st[a];
+      if (d_out) d_out[r] = D;
     }
   }
   return NONODE_OK;

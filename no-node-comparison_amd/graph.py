@@ -36,7 +36,10 @@ SEGNO(graph="any", trainable=True) train on it with nothing read back (harness.e
 segno_rollout_train_graph unroll a rollout on such graphs). Under a finite cut-off the builder can search a cell
 list instead of all the nodes of a graph (``method="cells"``, ``nonode_neighbor_graph_cells``): the same arrays bit
 for bit, O(cells the cut-off box touches) per receiver instead of O(N); ``method="auto"`` chooses by the size of
-the largest graph (``neighbor_method``).
+the largest graph (``neighbor_method``). ``method="knn_cells"`` (``nonode_neighbor_graph_knn_cells``) searches the
+same cell list with a radius found per receiver, so it also builds the pure k-NN graph (``r_cut=None``) and a
+graph under a loose cut-off without looking at every node: again the same arrays bit for bit; ``"knn_auto"``
+chooses between it and ``"brute"`` by the size.
 
 Graphs of mixed sizes in one batch (``RaggedBatch``, ``neighbor_graph_ragged``): the descriptor holds the sizes
 on the host and their prefix sum and node -> graph map on the device, uploaded once; the builder, the node
@@ -420,17 +423,33 @@ def neighbor_args(k, r_cut):
 # None would mean not measured, and "auto" would be "brute".
 CELLS_AUTO_MIN_NODES = 10000
 
+# method="knn_auto": the size of the largest graph from which the k-NN cell search ("knn_cells") is taken, for any
+# r_cut. Measured the same way (profiles/graph/bench_knn_cells.jsonl: uniform points,
+# k = 16, no cut-off): the smallest measured N from which "knn_cells" beat "brute" in every alternation there and
+# at every larger measured N. Measured on the MI355X: 10,000 (1.64 x there; at 4,000 and below, and at 8 x 1,000, the
+# cell list's five extra launches cost more than the search saves). None would mean no such size, and "knn_auto"
+# would be "brute".
+KNN_CELLS_AUTO_MIN_NODES = 10000
+
 
 def neighbor_method(method, r_cut, n_max=0):
-    """The search a neighbour-graph build runs, "brute" or "cells", from its method= argument, on the host and
-    before any device work. None / "brute": one wave per receiver over all the nodes of its graph (any r_cut).
-    "cells": the cell-list search, which needs a cut-off whose float32 square is finite (ValueError otherwise);
-    the same arrays, bit for bit. "auto": "cells" when such a cut-off is given and the largest graph has at
-    least CELLS_AUTO_MIN_NODES nodes, else "brute". Anything else: ValueError."""
+    """The search a neighbour-graph build runs, "brute", "cells" or "knn_cells", from its method= argument, on the
+    host and before any device work. None / "brute": one wave per receiver over all the nodes of its graph (any
+    r_cut). "cells": the cell-list search, which needs a cut-off whose float32 square is finite (ValueError
+    otherwise); the same arrays, bit for bit. "auto": "cells" when such a cut-off is given and the largest graph
+    has at least CELLS_AUTO_MIN_NODES nodes, else "brute". "knn_cells": the k-NN search on the cell list, which
+    finds its radius per receiver and so takes any r_cut, None included; the same arrays, bit for bit.
+    "knn_auto": "knn_cells" when the largest graph has at least KNN_CELLS_AUTO_MIN_NODES nodes, else "brute".
+    Anything else: ValueError."""
     if method is None or method == "brute":
         return "brute"
+    if method == "knn_cells":
+        return "knn_cells"
+    if method == "knn_auto":
+        return "knn_cells" if KNN_CELLS_AUTO_MIN_NODES is not None and n_max >= KNN_CELLS_AUTO_MIN_NODES else "brute"
     if method not in ("cells", "auto"):
-        raise ValueError(f'neighbor_graph: method must be None, "brute", "cells" or "auto", got {method!r}')
+        raise ValueError('neighbor_graph: method must be None, "brute", "cells", "auto", "knn_cells" or "knn_auto", '
+                         f"got {method!r}")
     finite = False
     if r_cut is not None:
         with np.errstate(over="ignore"):
@@ -475,7 +494,9 @@ def neighbor_graph(x, batch_size, n_nodes, k, r_cut=None, *, by_sender=False, me
     discrete function of x: nothing here is differentiable, and no gradient flows through it.
     method (neighbor_method): None / "brute" searches all N nodes per receiver; "cells" (a finite cut-off only)
     searches a cell list instead, one nonode_neighbor_graph_cells call, and returns the same arrays bit for bit,
-    faster on large graphs; "auto" chooses by the size."""
+    faster on large graphs; "auto" chooses by the size. "knn_cells" (any r_cut, None included) is the k-NN search
+    on the cell list, one nonode_neighbor_graph_knn_cells call, the same arrays bit for bit; "knn_auto" chooses
+    between it and "brute" by the size."""
     from . import _lib
     B, N = int(batch_size), int(n_nodes)
     k, r2 = neighbor_args(k, r_cut)
@@ -489,7 +510,8 @@ def neighbor_graph(x, batch_size, n_nodes, k, r_cut=None, *, by_sender=False, me
 def _build_neighbor_graph(x, k, r2, by_sender, B, N, batch, method="brute"):
     """The builder's call behind neighbor_graph (B graphs of N rows; batch None) and neighbor_graph_ragged
     (batch a RaggedBatch; B, N unused), after their host checks: outputs, workspace, one C call, and the CSR
-    by sender if asked. method "cells": the cell-list entry (equal sizes: null descriptors) in place of either."""
+    by sender if asked. method "cells" / "knn_cells": the cell-list entries (equal sizes: null descriptors) in place
+    of either."""
     from . import _lib
     x = _lib.f32(x)
     dev = x.device
@@ -498,13 +520,16 @@ def _build_neighbor_graph(x, k, r2, by_sender, B, N, batch, method="brute"):
     col, eid, rows = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
     L = _lib.lib()
     out = (_lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(eid), _lib.ptr(rows))
-    if method == "cells":
+    if method in ("cells", "knn_cells"):
         G, n_max = (B, N) if batch is None else (batch.n_graphs, batch.n_max)
         desc = (None, None) if batch is None else (batch.graph_ptr, batch.graph_of)
-        ws_bytes = L.nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k)
+        query, build = ((L.nonode_neighbor_graph_cells_workspace_bytes, L.nonode_neighbor_graph_cells)
+                        if method == "cells" else
+                        (L.nonode_neighbor_graph_knn_cells_workspace_bytes, L.nonode_neighbor_graph_knn_cells))
+        ws_bytes = query(G, n_total, n_max, k)
         ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
-        _lib.check(L.nonode_neighbor_graph_cells(G, n_total, n_max, k, cap, r2, _lib.ptr(desc[0]), _lib.ptr(desc[1]),
-                                                 _lib.ptr(x), *out, _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
+        _lib.check(build(G, n_total, n_max, k, cap, r2, _lib.ptr(desc[0]), _lib.ptr(desc[1]), _lib.ptr(x), *out,
+                         _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
     elif batch is None:
         ws_bytes = L.nonode_neighbor_graph_workspace_bytes(B, N, k)
         ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)

@@ -447,7 +447,8 @@ def prepare_inputs_graph(loc, vel, n_nodes, charges=None, t_in=None, *, k=None, 
     nonode_prepare_inputs_bwd_ragged. Same returns.
 
     neighbor_method (with k only): the search that builds the graph, graph.neighbor_graph's method= (None /
-    "brute", "cells" under a finite r_cut, "auto"): the same graph bit for bit, built faster on large graphs."""
+    "brute", "cells" under a finite r_cut, "auto"; "knn_cells" / "knn_auto" for any r_cut, None included): the same
+    graph bit for bit, built faster on large graphs."""
     _graph_source(k, r_cut, edges, "prepare_inputs_graph", neighbor_method)
     batch = None
     if sizes is not None:
@@ -625,7 +626,8 @@ def egno_rollout_graph(model, loc, vel, charges, n_nodes, batch_size, traj_len, 
     sizes (a graph.RaggedBatch or a host sequence; n_nodes and batch_size None): G graphs of mixed sizes in
     the one loop. loc, vel [n_total, 3], timesteps_in [G], timesteps_out shared (one row); loc_preds
     [traj_len*T, n_total, 3], energies [.., G, 1].
-    neighbor_method (with k): the search behind every segment's graph, as in prepare_inputs_graph."""
+    neighbor_method (with k): the search behind every segment's graph, as in prepare_inputs_graph ("knn_cells" /
+    "knn_auto" also without a cut-off, the drivers' default graph)."""
     from .egno import EGNO
     _general_model(model, EGNO, "egno_rollout_graph")
     if model.num_inputs > 1:
@@ -683,7 +685,8 @@ def egno_rollout_train_graph(model, loc, vel, charges, n_nodes, batch_size, traj
     nodes / edge_attr (detached, as the reference does at main_simulation_simple_no.py:333,338). No
     energies. Nothing in the loop or in the backward reads the device.
     sizes: G graphs of mixed sizes, as in egno_rollout_graph (loc, vel [n_total, 3], timesteps_in [G], shared
-    timesteps_out; the per-graph mean and its reverse are each graph's own). neighbor_method as there."""
+    timesteps_out; the per-graph mean and its reverse are each graph's own). neighbor_method as there ("knn_cells" /
+    "knn_auto" included)."""
     from . import graph as _graph
     from .egno import EGNO
     who = "egno_rollout_train_graph"
@@ -736,7 +739,8 @@ def segno_rollout_graph(model, loc, vel, charges, batch_size, traj_len, num_step
     with return_graphs=True also the list of the segments' graphs.
     sizes (a graph.RaggedBatch or a host sequence; batch_size None or len(sizes)): G graphs of mixed sizes in
     the one loop. loc, vel [n_total, 3]; energies [traj_len, G, 1].
-    neighbor_method (with k): the search behind every segment's graph, as in prepare_inputs_graph."""
+    neighbor_method (with k): the search behind every segment's graph, as in prepare_inputs_graph ("knn_cells" /
+    "knn_auto" also without a cut-off, the drivers' default graph)."""
     from .segno import SEGNO
     _general_model(model, SEGNO, "segno_rollout_graph")
     if model.bug_compat:
@@ -773,7 +777,8 @@ def segno_rollout_train_graph(model, loc, vel, charges, batch_size, traj_len, nu
     to the parameters and to the initial loc and vel. No gradient flows through the choice of neighbours (it is
     discrete) or through his = |v| and edge_attr (detached: the reference builds them from data,
     train_nbody.py:121-123,230-233, as egno_rollout_train_graph does). No energies. Nothing in the loop or in
-    the backward reads the device. sizes: G graphs of mixed sizes, and neighbor_method, as in segno_rollout_graph."""
+    the backward reads the device. sizes: G graphs of mixed sizes, and neighbor_method ("knn_cells" / "knn_auto"
+    included), as in segno_rollout_graph."""
     from . import graph as _graph
     from .segno import SEGNO
     who = "segno_rollout_train_graph"

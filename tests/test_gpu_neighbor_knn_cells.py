@@ -1,0 +1,227 @@
+"""GPU tests of the k-NN search on the cell list (graph.neighbor_graph / neighbor_graph_ragged with
+method="knn_cells", nonode_neighbor_graph_knn_cells).
+
+The contract is the brute-force builder's, bit for bit, for any r_cut (None included), so there is no tolerance
+anywhere: every array is compared with torch.equal against method="brute" on the same device, on the input
+families and sizes of tests/_knn_cells_cases.py (which tests/test_neighbor_knn_cells_options.py compares with the
+numpy reference on the CPU), as three equal-size graphs and as a mixed batch. Rollouts and a taped training step on
+a knn_cells-built graph are compared with torch.equal to the same call on the brute-built one.
+"""
+import numpy as np
+import pytest
+import torch
+
+import no_node_comparison_amd as pkg
+from no_node_comparison_amd import graph, harness
+from tests._knn_cells_cases import FAMILIES, RAGGED, cases, points
+from tests._neighbor_ref import cutoff_straddlers, neighbor_ref, tied_pairs
+from tests.conftest import load_golden, params_of
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+NAMES = ("row_ptr", "col", "rows", "eid")
+SENDER = ("srow_ptr", "seid", "valid")
+
+
+def _dev(a):
+    return torch.tensor(np.ascontiguousarray(a)).to(DEV)
+
+
+def _same_graph(a, b, sender=False):
+    for n in NAMES + (SENDER if sender else ()):
+        assert torch.equal(getattr(a, n), getattr(b, n)), n
+    assert a.capacity == b.capacity and a.n_nodes == b.n_nodes
+
+
+def _assert_ref(ng, ref):
+    got = {n: getattr(ng, n).cpu().numpy() for n in NAMES}
+    assert ng.capacity == ref["cap"] and int(got["row_ptr"][-1]) == ref["E"]
+    for n in NAMES:
+        assert got[n].dtype == np.int32 and np.array_equal(got[n], ref[n]), n
+
+
+# ---- 1. bitwise the brute-force builder's arrays ---------------------------------------------------------------
+BY_FAMILY = {fam: sorted({(c[2][0], c[3]) for c in cases() if c[1] == fam and len(c[2]) == 1}) for fam in FAMILIES}
+
+
+@pytest.mark.parametrize("fam", list(FAMILIES))
+def test_three_equal_graphs_equal_brute(fam):
+    """B = 3 graphs of N nodes at every (N, k) the CPU test takes for the family."""
+    checked = 0
+    for N, k in BY_FAMILY[fam]:
+        x, r_cut = points(fam, (N, N, N))
+        xd = _dev(x)
+        a = graph.neighbor_graph(xd, 3, N, k, r_cut, method="brute", by_sender=True)
+        b = graph.neighbor_graph(xd, 3, N, k, r_cut, method="knn_cells", by_sender=True)
+        _same_graph(a, b, sender=True)
+        assert isinstance(b, graph.NeighborGraph) and b.capacity == 3 * N * min(k, N - 1)
+        checked += int(b.n_edges.item())
+    assert checked > 0
+
+
+@pytest.mark.parametrize("fam", list(FAMILIES))
+def test_a_mixed_batch_equals_brute(fam):
+    x, r_cut = points(fam, RAGGED)
+    xd = _dev(x)
+    batch = graph.RaggedBatch(RAGGED, xd.device)
+    for k in (6, 64):
+        a = graph.neighbor_graph_ragged(xd, batch, k, r_cut, method="brute", by_sender=True)
+        b = graph.neighbor_graph_ragged(xd, batch, k, r_cut, method="knn_cells", by_sender=True)
+        _same_graph(a, b, sender=True)
+        assert b.n_nodes is None and b.batch is batch and b.capacity == batch.capacity(k)
+        deg = np.diff(b.row_ptr.cpu().numpy())
+        assert deg[0] == 0                                   # the graph of one node
+
+
+def test_distances_that_tie_only_when_no_operation_is_fused():
+    pairs = tied_pairs(16)
+    G = len(pairs)
+    x = np.zeros((G, 3, 3), dtype=np.float32)
+    for g, (a, b) in enumerate(pairs):
+        x[g, 1], x[g, 2] = a, b
+    xd = _dev(x.reshape(-1, 3))
+    for r_cut in (None, 4.0):
+        a = graph.neighbor_graph(xd, G, 3, 1, r_cut, method="brute")
+        b = graph.neighbor_graph(xd, G, 3, 1, r_cut, method="knn_cells")
+        _same_graph(a, b)
+        col, rp = b.col.cpu().numpy(), b.row_ptr.cpu().numpy()
+        assert all(col[rp[3 * g]] == 3 * g + 1 for g in range(G))      # the tie goes to the lower index
+    for pt, r_cut, cand in cutoff_straddlers(2):
+        xs = _dev(np.stack([np.zeros(3, dtype=np.float32), pt]))
+        b = graph.neighbor_graph(xs, 1, 2, 1, r_cut, method="knn_cells")
+        _same_graph(graph.neighbor_graph(xs, 1, 2, 1, r_cut, method="brute"), b)
+        assert int(b.n_edges.item()) == (2 if cand else 0)
+
+
+def test_one_graph_of_20000_nodes_equals_brute_and_repeats_bitwise():
+    """The uniform cube of tools/bench_graph.py --case knn_cells at N = 20,000 (g = 17), k = 16, no cut-off, and
+    under a loose one; built twice: the order in which the atomics filled the cells must not show."""
+    N = 20000
+    side = 10.0 * (N / 1000.0) ** (1.0 / 3.0)
+    xd = _dev((np.random.RandomState(7).rand(N, 3) * side).astype(np.float32))
+    for r_cut in (None, 3.6):
+        a = graph.neighbor_graph(xd, 1, N, 16, r_cut, method="brute", by_sender=True)
+        b = graph.neighbor_graph(xd, 1, N, 16, r_cut, method="knn_cells", by_sender=True)
+        c = graph.neighbor_graph(xd, 1, N, 16, r_cut, method="knn_cells", by_sender=True)
+        _same_graph(a, b, sender=True)
+        _same_graph(b, c, sender=True)
+        E = int(b.n_edges.item())
+        assert E == 16 * N if r_cut is None else 15 * N < E <= 16 * N      # (some 195 candidates per receiver)
+    want = "knn_cells" if graph.KNN_CELLS_AUTO_MIN_NODES is not None and N >= graph.KNN_CELLS_AUTO_MIN_NODES else "brute"
+    assert graph.neighbor_method("knn_auto", None, N) == want
+    _same_graph(a, graph.neighbor_graph(xd, 1, N, 16, 3.6, method="knn_auto", by_sender=True), sender=True)
+
+
+def test_knn_cells_repeat_bitwise_on_a_mixed_batch():
+    x, _ = points("gaussian", RAGGED, seed=3)
+    xd = _dev(x)
+    runs = [graph.neighbor_graph_ragged(xd, RAGGED, 16, None, method="knn_cells", by_sender=True) for _ in range(2)]
+    _same_graph(runs[0], runs[1], sender=True)
+    assert int(runs[0].n_edges.item()) > 0
+
+
+def test_brute_and_cells_still_match_the_numpy_reference():
+    """Their code did not change; one comparison each guards that."""
+    x, _ = points("gaussian", (200, 200))
+    xd = _dev(x)
+    _assert_ref(graph.neighbor_graph(xd, 2, 200, 8, None, method="brute"), neighbor_ref(x, 2, 200, 8, None))
+    ref = neighbor_ref(x, 2, 200, 8, 0.9)
+    assert 0 < ref["E"] < ref["cap"]
+    _assert_ref(graph.neighbor_graph(xd, 2, 200, 8, 0.9, method="cells"), ref)
+    _assert_ref(graph.neighbor_graph(xd, 2, 200, 8, 0.9, method="knn_cells"), ref)
+
+
+# ---- 2. rollouts and training on a knn_cells-built graph -----------------------------------------------------
+@pytest.fixture(scope="module")
+def egno_fx():
+    return load_golden("egno_fwd")
+
+
+@pytest.fixture(scope="module")
+def segno_fx():
+    return load_golden("segno_fwd")
+
+
+def _egno(fx, T=10, mode="any"):
+    m = pkg.EGNO(n_layers=4, in_node_nf=2, in_edge_nf=2, hidden_nf=64, with_v=True, num_modes=2, num_timesteps=T,
+                 time_emb_dim=32, device=DEV, graph=mode)
+    m.load_state_dict({k: torch.tensor(v) for k, v in params_of(fx).items()})
+    return m.eval() if mode == "any" else m.train()
+
+
+def _segno(fx):
+    m = pkg.SEGNO(in_node_nf=1, in_edge_nf=2, hidden_nf=64, n_layers=8, recurrent=True, device=DEV, graph="any")
+    m.load_state_dict({k: torch.tensor(v) for k, v in params_of(fx).items()})
+    return m.eval()
+
+
+def _rollout_inputs(B, N, seed):
+    rs = np.random.RandomState(seed)
+    loc = (rs.randn(B, N, 3) * 2.5).astype(np.float32)
+    vel = (rs.randn(B, N, 3) * 0.3).astype(np.float32)
+    q = rs.choice([-1.0, 1.0], size=(B, N, 1)).astype(np.float32)
+    return _dev(loc), _dev(vel), _dev(q)
+
+
+B_, N_, K_ = 1, 500, 6
+
+
+def _rollouts(me, ms, loc, vel, q, meth):
+    pe, en, _, ge = harness.egno_rollout_graph(me, loc, vel, q, N_, B_, 2, k=K_, energy_dataset="charged",
+                                               return_graphs=True, neighbor_method=meth)
+    ps, es, gs = harness.segno_rollout_graph(ms, loc.reshape(-1, 3), vel.reshape(-1, 3), q, B_, 2, [3, 4], k=K_,
+                                             energy_dataset="charged", return_graphs=True, neighbor_method=meth)
+    return pe, en, ps, es, ge + gs
+
+
+def test_rollouts_are_the_same_by_either_search_and_do_not_synchronise(egno_fx, segno_fx):
+    """B = 1, N = 500 (g = 5), k = 6, no cut-off, two segments: positions, energies and every segment's graph."""
+    loc, vel, q = _rollout_inputs(B_, N_, 3)
+    me, ms = _egno(egno_fx), _segno(segno_fx)
+    a = _rollouts(me, ms, loc, vel, q, "brute")
+    b = _rollouts(me, ms, loc, vel, q, "knn_cells")      # (also the warm-up of what follows)
+    torch.cuda.synchronize()
+    for u, v in zip(a[:4], b[:4]):
+        assert torch.equal(u, v)
+    assert len(a[4]) == len(b[4]) == 4
+    for ga, gb in zip(a[4], b[4]):
+        _same_graph(ga, gb)
+    assert torch.isfinite(b[0][:10]).all() and int(b[4][0].n_edges.item()) == N_ * K_
+    probe = torch.ones(1, device=DEV)
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        try:
+            probe.item()
+            raises = False
+        except RuntimeError:
+            raises = True
+        if raises:
+            _rollouts(me, ms, loc, vel, q, "knn_cells")
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    torch.cuda.synchronize()
+    assert raises, "torch.cuda.set_sync_debug_mode('error') does not raise on .item() in this torch build"
+
+
+def test_a_taped_training_step_on_a_knn_cells_graph_equals_the_brute_one(egno_fx):
+    """prepare_inputs_graph(tape=True, neighbor_method="knn_cells") into EGNO(graph="trainable"): the outputs, the
+    parameter gradients and the gradients of loc and vel torch.equal to those on the brute-built graph."""
+    B, N, k = 2, 108, 6
+    loc, vel, q = _rollout_inputs(B, N, 5)
+    m = _egno(egno_fx, mode="trainable")
+    res = {}
+    for meth in ("brute", "knn_cells"):
+        m.zero_grad(set_to_none=True)
+        lg, vg = loc.clone().requires_grad_(True), vel.clone().requires_grad_(True)
+        x, v, ea, nodes, lm, g = harness.prepare_inputs_graph(lg, vg, N, q, k=k, tape=True, neighbor_method=meth)
+        assert isinstance(g, graph.NeighborGraph) and g.has_sender_csr()
+        out = m(x, nodes, g, ea, v=v, loc_mean=lm)
+        sum(o.square().mean() for o in out).backward()
+        res[meth] = ([o.detach().clone() for o in out], [p.grad.clone() for p in m.parameters() if p.grad is not None],
+                     [lg.grad.clone(), vg.grad.clone()], g)
+    torch.cuda.synchronize()
+    a, b = res["brute"], res["knn_cells"]
+    _same_graph(a[3], b[3], sender=True)
+    assert len(a[1]) == len(b[1]) > 0
+    for u, w in zip(a[0] + a[1] + a[2], b[0] + b[1] + b[2]):
+        assert torch.isfinite(u).all() and torch.equal(u, w)

@@ -1,7 +1,7 @@
 """Timings of the general-graph path (EGNO graph="any", csrc/nonode_graph.hip) on the GPU. One JSON
 line per case on stdout (DESIGN.md section 3.7 quotes them; raw lines under profiles/graph/).
 
-python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|ragged_rollout|knn_rollout_train|segno_train|cells|cells_rollout|all] [--reps 7] [--iters 20] [--arm both|ours]
+python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|ragged_rollout|knn_rollout_train|segno_train|cells|cells_rollout|knn_cells|knn_cells_rollout|all] [--reps 7] [--iters 20] [--arm both|ours]
 
   price  the C2 graph (B = 512, N = 20, T = 10: 5120 fully connected graphs per layer launch) through
          the fused layer entry (nonode_egnn_layer) and, passed as an edge list, through the general one
@@ -46,6 +46,11 @@ python tools/bench_graph.py [--case price|knn|knn_train|knn_rollout|ragged_rollo
          8 x 1000; one line per shape, with whether the two gave the same arrays.
   cells_rollout  knn_rollout under that cut-off at 8 x 1000 and 1 x 20,000, the graph rebuilt every segment by
          either search (harness.egno_rollout_graph(neighbor_method=...)), alternated likewise.
+  knn_cells  the builder alone on the pure k-NN graph (r_cut=None, k = 16, the same cubes and shapes): method="brute"
+         against the k-NN search on the cell list (method="knn_cells"), alternated likewise, one line per shape;
+         and one line under a loose cut-off (r_cut = 3.6, some 195 candidates per receiver) at 1 x 50,000,
+         method="cells" against "knn_cells".
+  knn_cells_rollout  cells_rollout without the cut-off at 1 x 20,000, "brute" against "knn_cells".
 Times are device events around `iters` back-to-back calls after a warm-up; each case reports the median
 over the reps and the spread (min, max) beside it.
 """
@@ -575,10 +580,73 @@ def case_cells_rollout(args):
     return out
 
 
+KNN_LOOSE_RCUT = 3.6   # about 195 candidates per receiver in the uniform cube (one node per unit volume)
+
+
+def _knn_cells_line(args, B, N, r_cut, base, label):
+    """One line of case knn_cells: the builder alone, method `base` against "knn_cells", alternated."""
+    x, side = uniform_cube(B, N, 7)
+    arms = {m: (lambda m=m: graph.neighbor_graph(x, B, N, CELLS_K, r_cut, method=m)) for m in (base, "knn_cells")}
+    a, b = arms[base](), arms["knn_cells"]()
+    same = all(torch.equal(getattr(a, n), getattr(b, n)) for n in ("row_ptr", "col", "rows", "eid"))
+    E = int(a.n_edges.item())
+    iters = args.iters if N <= 20000 else max(args.iters // 4, 3)
+    t = alternate(arms, args.reps, iters)
+    ba, kc = stats(t[base]), stats(t["knn_cells"])
+    return {"case": "knn_cells", "row": label,
+            "shape": {"graphs": B, "nodes_per_graph": N, "k": CELLS_K, "r_cut": r_cut, "cube_side": side,
+                      "cells_per_axis": max(g for g in range(1, 700) if 4 * g ** 3 <= max(N, 4))},
+            "iters_per_rep": iters, "mean_degree": E / (B * N), "baseline": base, "knn_cells_bitwise_equal_to_baseline": same,
+            base: ba, "knn_cells": kc, base + "_per_rep_ms": t[base], "knn_cells_per_rep_ms": t["knn_cells"],
+            "speedup": ba["median_ms"] / kc["median_ms"],
+            "knn_cells_faster_on_every_alternation": all(c < b_ for b_, c in zip(t[base], t["knn_cells"]))}
+
+
+def case_knn_cells(args):
+    """The builder alone on the pure k-NN graph (k = 16, r_cut=None, the uniform cube of case cells): method="brute"
+    against method="knn_cells", one line per shape; then one line under a loose cut-off at 1 x 50,000, where the
+    cut-off's own cell search (method="cells") walks a box of some 200 candidates per receiver, against "knn_cells"."""
+    out = [_knn_cells_line(args, B, N, None, "brute", "pure k-NN") for B, N in CELLS_SHAPES]
+    out.append(_knn_cells_line(args, 1, 50000, KNN_LOOSE_RCUT, "cells", "loose cut-off"))
+    return out
+
+
+def case_knn_cells_rollout(args):
+    """cells_rollout without the cut-off at 1 x 20,000 (k = 16, traj_len = 4, the damped heads): the graph rebuilt
+    every segment by the brute-force search or by "knn_cells", alternated."""
+    T, SEG, DAMP = 10, 4, 0.01
+    B, N = 1, 20000
+    x, side = uniform_cube(B, N, 9)
+    loc = x.reshape(B, N, 3)
+    _, vel, q = synthetic(B, N, 2)
+    t_out = torch.arange(1, T * SEG + 1, device=DEV).repeat(B, 1)
+    m = model(T, graph="any")
+    with torch.no_grad():
+        for layer in m.layers:
+            for head in (layer.coord_net, layer.node_v_net):
+                head.mlp[2].weight.mul_(DAMP)
+                head.mlp[2].bias.mul_(DAMP)
+    arms = {meth: (lambda meth=meth: harness.egno_rollout_graph(
+        m, loc, vel, q, N, B, SEG, k=CELLS_K, timesteps_out=t_out, neighbor_method=meth)[0])
+        for meth in ("brute", "knn_cells")}
+    a, b = arms["brute"](), arms["knn_cells"]()
+    same = bool(torch.equal(a, b))
+    iters = max(args.iters // 4, 3)
+    t = alternate(arms, args.reps, iters)
+    br, kc = stats(t["brute"]), stats(t["knn_cells"])
+    return {"case": "knn_cells_rollout", "shape": {"graphs": B, "nodes_per_graph": N, "k": CELLS_K, "r_cut": None,
+                                                   "cube_side": side, "T": T, "layers": 4, "traj_len": SEG},
+            "iters_per_rep": iters, "model": f"untrained, last layers of coord_net and node_v_net scaled by {DAMP}",
+            "positions_bitwise_equal": same, "last_frame_finite": bool(torch.isfinite(a[-1]).all()),
+            "brute": br, "knn_cells": kc, "brute_per_rep_ms": t["brute"], "knn_cells_per_rep_ms": t["knn_cells"],
+            "speedup": br["median_ms"] / kc["median_ms"],
+            "knn_cells_faster_on_every_alternation": all(c < b_ for b_, c in zip(t["brute"], t["knn_cells"]))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="all", choices=["price", "knn", "knn_train", "knn_rollout", "ragged_rollout", "knn_rollout_train", "segno_train",
-                                                    "cells", "cells_rollout", "all"])
+                                                    "cells", "cells_rollout", "knn_cells", "knn_cells_rollout", "all"])
     ap.add_argument("--arm", default="both", choices=["both", "ours"], help="knn_train, knn_rollout, knn_rollout_train, segno_train: the HIP arm alone")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
@@ -588,7 +656,8 @@ def main():
     for name, fn in (("price", case_price), ("knn", case_knn), ("knn_train", case_knn_train),
                      ("knn_rollout", case_knn_rollout), ("ragged_rollout", case_ragged_rollout),
                      ("knn_rollout_train", case_knn_rollout_train),
-                     ("segno_train", case_segno_train), ("cells", case_cells), ("cells_rollout", case_cells_rollout)):
+                     ("segno_train", case_segno_train), ("cells", case_cells), ("cells_rollout", case_cells_rollout),
+                     ("knn_cells", case_knn_cells), ("knn_cells_rollout", case_knn_cells_rollout)):
         if args.case in (name, "all"):
             res = fn(args)
             for line in res if isinstance(res, list) else [res]:
