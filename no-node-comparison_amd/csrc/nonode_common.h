@@ -701,7 +701,7 @@ __device__ __forceinline__ void mm64_scaled(f4 (&acc)[4], const h8* wh, const f4
 struct GraphRows {
   int r0, n;
 };
-__device__ __forceinline__ GraphRows graph_rows(const int* __restrict__ graph_ptr, int b, int N, int n_total) {
+__host__ __device__ __forceinline__ GraphRows graph_rows(const int* __restrict__ graph_ptr, int b, int N, int n_total) {
   if (!graph_ptr) return GraphRows{b * N, N};
   const int lo = imin(imax(graph_ptr[b], 0), n_total), hi = imin(imax(graph_ptr[b + 1], 0), n_total);
   return GraphRows{lo, hi - lo};

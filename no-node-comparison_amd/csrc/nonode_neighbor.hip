@@ -17,10 +17,11 @@
 //   cell_bbox / _count / _fill_kernel, neighbor_select_cells_kernel  the same rows under a finite cut-off from
 //                           a cell list (nonode_neighbor_graph_cells): each graph's nodes binned into a
 //                           uniform grid and sorted by cell, one wave per receiver over the cells its cut-off
-//                           box touches, the candidates through the same keep-the-k-smallest body
+//                           box touches
 //   neighbor_select_knn_cells_kernel  the same rows for ANY r2_max (+inf: the pure k-NN graph) from the same cell
 //                           list (nonode_neighbor_graph_knn_cells): a box of cells that holds k other nodes bounds
 //                           the k-th distance, and the cut-off search with that bound finds the rest
+//                           (every search: candidate_key, topk_chunk; both cell searches: walk_segments)
 //   (scan)                  row_ptr = exclusive prefix sum of the degrees (nonode_graph.hip's
 //                           one-workgroup scan)
 //   neighbor_compact_kernel fixed-pitch rows -> CSR (col, rows, eid), and the -1 tail
@@ -80,6 +81,12 @@ __host__ __device__ __forceinline__ float dist2(float a0, float a1, float a2, fl
   const float d0 = a0 - b0, d1 = a1 - b1, d2 = a2 - b2;
   return ((d0 * d0) + (d1 * d1)) + (d2 * d2);
 }
+// THE key of sender j (index inside its graph) at distance d2 from receiver i: the total order (d2, j) every search
+// keeps the smallest of; KEY_NONE for a non-candidate (the receiver itself, a distance above r2_max or NaN).
+// d2 >= +0 where the compare holds (a NaN fails it), so its bits order as an unsigned integer.
+__host__ __device__ __forceinline__ u64 candidate_key(float d2, int j, int i, float r2_max) {
+  return j != i && d2 <= r2_max ? ((u64)__builtin_bit_cast(unsigned, d2) << 32) | (unsigned)j : KEY_NONE;
+}
 
 // The keep-the-k-smallest body both searches share. Lane l of `best` holds the l-th smallest key seen so far
 // (ascending). Of a chunk of 64 candidate keys (KEY_NONE: none in that lane) only the keys below the kk-th
@@ -121,52 +128,8 @@ __device__ __forceinline__ void topk_write(u64 best, int kk, int lane, int r, in
   if (lane == 0) deg[r] = d;
 }
 
-// One wave per receiver r = g0 + i of a graph of N rows from g0 on, striding over all N nodes of its graph
-// (the brute-force search: any r2_max, +inf included). kk = min(k, N - 1); the chunks go through topk_chunk.
-// tmp [n_total][pitch]: the row's senders (global index) ascending; deg [n_total].
-// The receiver's graph: graph_of null, equal sizes (g0 = (r / n_each) n_each, N = n_each); otherwise graph
-// g = graph_of[r] of n_graphs, rows graph_ptr[g] .. graph_ptr[g + 1] (graph_rows holds them to
-// [0, n_total], and kk to the pitch, so nothing below leaves x, tmp or deg whatever the descriptor says).
-// g0, N and kk are the same in every lane and kept in scalar registers.
-__global__ __launch_bounds__(256) void neighbor_select_kernel(int n_total, int n_each, int k, int pitch, float r2_max,
-                                                              int n_graphs, const int* __restrict__ graph_ptr,
-                                                              const int* __restrict__ graph_of,
-                                                              const float* __restrict__ x, int* __restrict__ tmp,
-                                                              int* __restrict__ deg) {
-  const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= n_total) return;   // (wave-uniform)
-  GraphRows gr{(r / n_each) * n_each, n_each};
-  if (graph_of) gr = graph_rows(graph_ptr, imin(imax(graph_of[r], 0), n_graphs - 1), 0, n_total);
-  const int g0 = __builtin_amdgcn_readfirstlane(gr.r0), N = __builtin_amdgcn_readfirstlane(gr.n);
-  const int kk = imin(imin(k, N - 1), pitch), i = r - g0;
-  if (kk <= 0) {   // a graph of one node: no pair (wave-uniform)
-    if (lane == 0) deg[r] = 0;
-    return;
-  }
-  const float xi0 = x[(size_t)r * 3 + 0], xi1 = x[(size_t)r * 3 + 1], xi2 = x[(size_t)r * 3 + 2];
-  u64 best = KEY_NONE;
-  for (int base = 0; base < N; base += 64) {
-    const int j = base + lane;
-    u64 key = KEY_NONE;
-    if (j < N && j != i) {
-      const size_t s = (size_t)(g0 + j) * 3;
-      const float d2 = dist2(xi0, xi1, xi2, x[s + 0], x[s + 1], x[s + 2]);
-      // d2 >= +0 here (a NaN fails the compare), so its bits order as an unsigned integer
-      if (d2 <= r2_max) key = ((u64)__float_as_uint(d2) << 32) | (unsigned)j;
-    }
-    topk_chunk(best, key, kk, lane);
-  }
-  topk_write(best, kk, lane, r, g0, pitch, tmp, deg);
-}
-
-// ---- the cell-list search (a finite r2_max): the same rows from the cells a receiver's cut-off box touches ----
-// nonode_cells.h has the grid rule, the binning function, the search box and why they miss no candidate.
-// Graph gi of a batch (rows g0 .. g0 + N) owns the N + 1 entries from g0 + gi on of one table of
-// n_total + n_graphs entries: its g^3 <= N / CELL_FILL cells, z fastest, then the bucket of its non-finite
-// nodes. Counts and slot claims are integer atomics, so the order of the nodes inside a cell differs from run
-// to run; that cannot show in the result, as a row is the top k of a SET of keys under a total order
-// (topk_chunk), then sorted by sender. Every index below is held inside its array whatever the descriptor says.
+// The graph of node r: graph_of null, equal sizes (graph gi = r / n_each, rows gi n_each .. + n_each); otherwise
+// graph gi = graph_of[r] of n_graphs, rows graph_ptr[gi] .. graph_ptr[gi + 1] (graph_rows holds them to [0, n_total]).
 struct NodeGraph {
   int gi, g0, n;
 };
@@ -177,6 +140,63 @@ __device__ __forceinline__ NodeGraph node_graph(int r, int n_total, int n_each, 
   const GraphRows gr = graph_rows(graph_ptr, gi, 0, n_total);
   return NodeGraph{gi, gr.r0, gr.n};
 }
+
+// The receiver of a wave, r = g0 + i of graph gi (N rows from g0 on), kk = min(k, N - 1) held to the pitch, so
+// nothing leaves x, tmp or deg whatever the descriptor says. gi, g0, N and kk are wave-uniform, in scalar registers.
+struct Receiver {
+  int r, gi, g0, N, kk, i;
+  float x[3];   // its coordinates
+};
+// everything but the coordinates. False: a graph of one node, the row's degree 0 is written, the wave is done.
+__device__ __forceinline__ bool receiver_rows(Receiver& rc, int r, int lane, int n_total, int n_each, int k, int pitch,
+                                              int n_graphs, const int* __restrict__ graph_ptr,
+                                              const int* __restrict__ graph_of, int* __restrict__ deg) {
+  const NodeGraph ng = node_graph(r, n_total, n_each, n_graphs, graph_ptr, graph_of);
+  rc.r = r;
+  rc.gi = __builtin_amdgcn_readfirstlane(ng.gi);
+  rc.g0 = __builtin_amdgcn_readfirstlane(ng.g0);
+  rc.N = __builtin_amdgcn_readfirstlane(ng.n);
+  rc.kk = imin(imin(k, rc.N - 1), pitch);
+  rc.i = r - rc.g0;
+  if (rc.kk > 0) return true;
+  if (lane == 0) deg[r] = 0;
+  return false;
+}
+
+// One wave per receiver, striding over all N nodes of its graph (the brute-force search: any r2_max, +inf
+// included); the chunks go through topk_chunk.
+// tmp [n_total][pitch]: the row's senders (global index) ascending; deg [n_total].
+__global__ __launch_bounds__(256) void neighbor_select_kernel(int n_total, int n_each, int k, int pitch, float r2_max,
+                                                              int n_graphs, const int* __restrict__ graph_ptr,
+                                                              const int* __restrict__ graph_of,
+                                                              const float* __restrict__ x, int* __restrict__ tmp,
+                                                              int* __restrict__ deg) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n_total) return;   // (wave-uniform)
+  Receiver rc;
+  if (!receiver_rows(rc, r, lane, n_total, n_each, k, pitch, n_graphs, graph_ptr, graph_of, deg)) return;
+  const float xi0 = x[(size_t)r * 3 + 0], xi1 = x[(size_t)r * 3 + 1], xi2 = x[(size_t)r * 3 + 2];
+  u64 best = KEY_NONE;
+  for (int base = 0; base < rc.N; base += 64) {
+    const int j = base + lane;
+    u64 key = KEY_NONE;
+    if (j < rc.N && j != rc.i) {   // (its own row is not read)
+      const size_t s = (size_t)(rc.g0 + j) * 3;
+      key = candidate_key(dist2(xi0, xi1, xi2, x[s + 0], x[s + 1], x[s + 2]), j, rc.i, r2_max);
+    }
+    topk_chunk(best, key, rc.kk, lane);
+  }
+  topk_write(best, rc.kk, lane, r, rc.g0, pitch, tmp, deg);
+}
+
+// ---- the cell-list search (a finite r2_max): the same rows from the cells a receiver's cut-off box touches ----
+// nonode_cells.h has the grid rule, the binning function, the search box and why they miss no candidate.
+// Graph gi of a batch (rows g0 .. g0 + N) owns the N + 1 entries from g0 + gi on of one table of
+// n_total + n_graphs entries: its g^3 <= N / CELL_FILL cells, z fastest, then the bucket of its non-finite
+// nodes. Counts and slot claims are integer atomics, so the order of the nodes inside a cell differs from run
+// to run; that cannot show in the result, as a row is the top k of a SET of keys under a total order
+// (topk_chunk), then sorted by sender. Every index below is held inside its array whatever the descriptor says.
 
 // bb [n_graphs][6], zero before: every graph's bounding box over its finite nodes as integer-ordered maxima
 // (cell_grid reads it back). A wave whose 64 nodes belong to one graph reduces first and sends six atomics.
@@ -245,78 +265,18 @@ __global__ __launch_bounds__(256) void cell_fill_kernel(int n_total, const float
     sorted[slot] = f4{x[(size_t)r * 3 + 0], x[(size_t)r * 3 + 1], x[(size_t)r * 3 + 2], __int_as_float(r)};
 }
 
-// One wave per receiver, taken in sorted order (neighbouring waves walk the same cells). With z the fastest
-// cell index, the cells (cx, cy, z_lo .. z_hi) of the receiver's box are one contiguous run of the sorted order:
-// cell_start[first cell] .. cell_start[last cell + 1]. A run holds about a third of a wave at cut-off-wide cells,
-// so the 64 lanes take several runs at once: groups of 16 lanes (32 with two or three runs, all 64 with one)
-// each stride over one run, and every round's 64 keys are one chunk of topk_chunk. Same dist2, same key
-// (d2, j) with j the node's index inside its graph, as in neighbor_select_kernel.
-// (NONODE_CELLS_PACK=0 builds give every run all 64 lanes, one run per round: the A/B of DESIGN.md section 3.7.1.)
-#ifndef NONODE_CELLS_PACK
-#define NONODE_CELLS_PACK 1
-#endif
-__global__ __launch_bounds__(256) void neighbor_select_cells_kernel(
-    int n_total, int n_each, int k, int pitch, float r2_max, float rr, int n_graphs, const int* __restrict__ graph_ptr,
-    const int* __restrict__ graph_of, const f4* __restrict__ sorted, const int* __restrict__ cell_start,
-    const unsigned* __restrict__ bb, int* __restrict__ tmp, int* __restrict__ deg) {
-  const int lane = threadIdx.x & 63;
-  const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (s >= n_total) return;   // (wave-uniform)
-  const f4 me = sorted[s];
-  const int r = __builtin_amdgcn_readfirstlane(__float_as_int(me[3]));
-  if (r < 0 || r >= n_total) return;   // (the fill wrote every slot: never)
-  const NodeGraph ng = node_graph(r, n_total, n_each, n_graphs, graph_ptr, graph_of);
-  const int g0 = __builtin_amdgcn_readfirstlane(ng.g0), N = __builtin_amdgcn_readfirstlane(ng.n);
-  const int gi = __builtin_amdgcn_readfirstlane(ng.gi);
-  const int kk = imin(imin(k, N - 1), pitch), i = r - g0;
-  const float xi0 = me[0], xi1 = me[1], xi2 = me[2];
-  if (kk <= 0 || !cell_finite(xi0, xi1, xi2)) {   // a graph of one node, a non-finite receiver: no pair
-    if (lane == 0) deg[r] = 0;
-    return;
-  }
-  const CellGrid cg = cell_grid(bb + (size_t)gi * 6, N, rr);
-  const CellBox bx = cell_box(cg, xi0, xi1, xi2, rr);
-  const int g = cg.g, tab = g0 + gi, last = n_total + n_graphs - 1;
-  const int ny = __builtin_amdgcn_readfirstlane(bx.hi[1] - bx.lo[1] + 1);
-  const int nruns = __builtin_amdgcn_readfirstlane((bx.hi[0] - bx.lo[0] + 1) * ny);
-  const int sh = !NONODE_CELLS_PACK ? 6 : (nruns >= 4 ? 4 : (nruns >= 2 ? 5 : 6));   // log2 of the lanes per run
-  const int grp = lane >> sh, sub = lane & ((1 << sh) - 1);
-  u64 best = KEY_NONE;
-  for (int u0 = 0; u0 < nruns; u0 += 64 >> sh) {
-    const int u = u0 + grp;
-    int p = 0, e = 0;
-    if (u < nruns) {
-      const int c = ((bx.lo[0] + u / ny) * g + bx.lo[1] + u % ny) * g;
-      p = cell_start[imin(tab + c + bx.lo[2], last)] + sub;
-      e = cell_start[imin(tab + c + bx.hi[2], last) + 1];
-    }
-    e = imin(e, n_total);
-    while (__any(p < e)) {
-      u64 key = KEY_NONE;
-      if (p >= 0 && p < e) {
-        const f4 o = sorted[p];
-        const int j = __float_as_int(o[3]) - g0;
-        const float d2 = dist2(xi0, xi1, xi2, o[0], o[1], o[2]);
-        // d2 >= +0 here (a NaN fails the compare), so its bits order as an unsigned integer
-        if (j != i && d2 <= r2_max) key = ((u64)__float_as_uint(d2) << 32) | (unsigned)j;
-      }
-      topk_chunk(best, key, kk, lane);
-      p += 1 << sh;
-    }
-  }
-  topk_write(best, kk, lane, r, g0, pitch, tmp, deg);
-}
+// Both searches on the cell list run one wave per receiver, taken in sorted order (neighbouring waves walk the same
+// cells), the receiver and its coordinates from the wave's slot. Their preamble is receiver_rows' written out in
+// each kernel: behind a function that returns whether to go on, both kernels measured 0.1 - 0.3 % slower from
+// 10,000 nodes on; written out they take the parent's time.
 
-// ---- the k-NN search on the cell list (any r2_max, +inf included): the radius is found per receiver ----
-// nonode_cells.h has the two phases, why they are exact and when a receiver walks its whole graph instead.
-// Same grid kernels as above (built with rr = 0: the width is extent / g), same dist2, same keys, same topk.
-
-// nseg segments of the sorted order through topk_chunk, segment u = sorted[p .. e) from seg(u, p, e): the lanes
-// take several segments at once, as neighbor_select_cells_kernel's do (groups of 16, 32 or all 64 lanes).
+// THE candidate walk: nseg segments of the sorted order, segment u = sorted[p .. e) from seg(u, p, e) (p = e = 0
+// before: an empty one). A segment holds about a third of a wave at cut-off-wide cells, so the 64 lanes take several
+// at once: groups of 16 lanes (32 with two or three segments, all 64 with one) each stride over one segment, and every
+// round's 64 keys are one chunk of topk_chunk. Same dist2 and key as neighbor_select_kernel.
 template <class Seg>
-__device__ __forceinline__ void walk_segments(u64& best, int nseg, Seg seg, int n_total, int kk, int lane, int i,
-                                              int g0, float r2_max, float xi0, float xi1, float xi2,
-                                              const f4* __restrict__ sorted) {
+__device__ __forceinline__ void walk_segments(u64& best, int nseg, Seg seg, const Receiver& rc, int n_total, int lane,
+                                              float r2_max, const f4* __restrict__ sorted) {
   const int sh = nseg >= 4 ? 4 : (nseg >= 2 ? 5 : 6);   // log2 of the lanes per segment
   const int grp = lane >> sh, sub = lane & ((1 << sh) - 1);
   for (int u0 = 0; u0 < nseg; u0 += 64 >> sh) {
@@ -329,16 +289,30 @@ __device__ __forceinline__ void walk_segments(u64& best, int nseg, Seg seg, int 
       u64 key = KEY_NONE;
       if (p >= 0 && p < e) {
         const f4 o = sorted[p];
-        const int j = __float_as_int(o[3]) - g0;
-        const float d2 = dist2(xi0, xi1, xi2, o[0], o[1], o[2]);
-        // d2 >= +0 here (a NaN fails the compare), so its bits order as an unsigned integer
-        if (j != i && d2 <= r2_max) key = ((u64)__float_as_uint(d2) << 32) | (unsigned)j;
+        key = candidate_key(dist2(rc.x[0], rc.x[1], rc.x[2], o[0], o[1], o[2]), __float_as_int(o[3]) - rc.g0, rc.i,
+                            r2_max);
       }
-      topk_chunk(best, key, kk, lane);
+      topk_chunk(best, key, rc.kk, lane);
       p += 1 << sh;
     }
   }
 }
+// A graph's part of cell_start (entries tab on, held below last). With z the fastest cell index, the cells
+// (cx, cy, z_lo .. z_hi) of a box are one run of the sorted order: cell_start[first cell] .. cell_start[last cell + 1].
+struct CellTable {
+  const int* __restrict__ cell_start;
+  int tab, last, g;
+  __device__ __forceinline__ void cells(const CellSeg& sg, int& p, int& e) const {
+    p = cell_start[imin(tab + sg.c0, last)];
+    e = cell_start[imin(tab + sg.c1, last) + 1];
+  }
+  // every run of box b
+  __device__ __forceinline__ void walk_box(u64& best, const CellBox& b, const Receiver& rc, int n_total, int lane,
+                                           float r2_max, const f4* __restrict__ sorted) const {
+    walk_segments(best, box_runs(b), [&](int u, int& p, int& e) { cells(box_run(b, u, g), p, e); }, rc, n_total, lane,
+                  r2_max, sorted);
+  }
+};
 __device__ __forceinline__ CellBox uniform_box(const CellBox& b) {   // the same in every lane: scalar registers
   CellBox u;
 #pragma unroll
@@ -349,12 +323,43 @@ __device__ __forceinline__ CellBox uniform_box(const CellBox& b) {   // the same
   return u;
 }
 
-// One wave per receiver, in sorted order. Every branch below is wave-uniform (all lanes hold the same receiver).
-// (NONODE_KNN_REWALK=1 builds drop phase 1's keys and walk the whole of box 2 where it leaves the shell box, in
-// place of the cells outside it alone: the A/B of DESIGN.md section 3.7.2.)
-#ifndef NONODE_KNN_REWALK
-#define NONODE_KNN_REWALK 0
-#endif
+// The cut-off search: the runs of the receiver's cut-off box.
+__global__ __launch_bounds__(256) void neighbor_select_cells_kernel(
+    int n_total, int n_each, int k, int pitch, float r2_max, float rr, int n_graphs, const int* __restrict__ graph_ptr,
+    const int* __restrict__ graph_of, const f4* __restrict__ sorted, const int* __restrict__ cell_start,
+    const unsigned* __restrict__ bb, int* __restrict__ tmp, int* __restrict__ deg) {
+  const int lane = threadIdx.x & 63;
+  const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= n_total) return;   // (wave-uniform)
+  const f4 me = sorted[s];
+  const int r = __builtin_amdgcn_readfirstlane(__float_as_int(me[3]));
+  if (r < 0 || r >= n_total) return;   // (the fill wrote every slot: never)
+  const NodeGraph ng = node_graph(r, n_total, n_each, n_graphs, graph_ptr, graph_of);
+  Receiver rc;
+  rc.r = r;
+  rc.g0 = __builtin_amdgcn_readfirstlane(ng.g0); rc.N = __builtin_amdgcn_readfirstlane(ng.n);
+  rc.gi = __builtin_amdgcn_readfirstlane(ng.gi);
+  rc.kk = imin(imin(k, rc.N - 1), pitch); rc.i = r - rc.g0;
+  if (rc.kk <= 0) {   // a graph of one node: no pair
+    if (lane == 0) deg[r] = 0;
+    return;
+  }
+  rc.x[0] = me[0]; rc.x[1] = me[1]; rc.x[2] = me[2];
+  if (!cell_finite(rc.x[0], rc.x[1], rc.x[2])) {   // a non-finite receiver: no pair
+    if (lane == 0) deg[rc.r] = 0;
+    return;
+  }
+  const CellGrid cg = cell_grid(bb + (size_t)rc.gi * 6, rc.N, rr);
+  const CellTable ct{cell_start, rc.g0 + rc.gi, n_total + n_graphs - 1, cg.g};
+  u64 best = KEY_NONE;
+  ct.walk_box(best, uniform_box(cell_box(cg, rc.x[0], rc.x[1], rc.x[2], rr)), rc, n_total, lane, r2_max, sorted);
+  topk_write(best, rc.kk, lane, rc.r, rc.g0, pitch, tmp, deg);
+}
+
+// ---- the k-NN search on the cell list (any r2_max, +inf included): the radius is found per receiver ----
+// nonode_cells.h has the two phases, why they are exact and when a receiver walks its whole graph instead.
+// Same grid kernels as above (built with rr = 0: the width is extent / g), same walk.
+// Every branch below is wave-uniform (all lanes hold the same receiver).
 __global__ __launch_bounds__(256) void neighbor_select_knn_cells_kernel(
     int n_total, int n_each, int k, int pitch, float r2_max, int n_graphs, const int* __restrict__ graph_ptr,
     const int* __restrict__ graph_of, const f4* __restrict__ sorted, const int* __restrict__ cell_start,
@@ -366,20 +371,24 @@ __global__ __launch_bounds__(256) void neighbor_select_knn_cells_kernel(
   const int r = __builtin_amdgcn_readfirstlane(__float_as_int(me[3]));
   if (r < 0 || r >= n_total) return;   // (the fill wrote every slot: never)
   const NodeGraph ng = node_graph(r, n_total, n_each, n_graphs, graph_ptr, graph_of);
-  const int g0 = __builtin_amdgcn_readfirstlane(ng.g0), N = __builtin_amdgcn_readfirstlane(ng.n);
-  const int gi = __builtin_amdgcn_readfirstlane(ng.gi);
-  const int kk = imin(imin(k, N - 1), pitch), i = r - g0;
-  if (kk <= 0) {   // a graph of one node: no pair
+  Receiver rc;
+  rc.r = r;
+  rc.g0 = __builtin_amdgcn_readfirstlane(ng.g0); rc.N = __builtin_amdgcn_readfirstlane(ng.n);
+  rc.gi = __builtin_amdgcn_readfirstlane(ng.gi);
+  rc.kk = imin(imin(k, rc.N - 1), pitch); rc.i = r - rc.g0;
+  if (rc.kk <= 0) {   // a graph of one node: no pair
     if (lane == 0) deg[r] = 0;
     return;
   }
-  const float xi0 = me[0], xi1 = me[1], xi2 = me[2];
-  const int tab = g0 + gi, last = n_total + n_graphs - 1;
+  rc.x[0] = me[0]; rc.x[1] = me[1]; rc.x[2] = me[2];
+  const float xi0 = rc.x[0], xi1 = rc.x[1], xi2 = rc.x[2];
+  const int kk = rc.kk;
   u64 best = KEY_NONE;
-  bool whole = !cell_finite(xi0, xi1, xi2) || kk >= N - 1;
+  bool whole = !cell_finite(xi0, xi1, xi2) || kk >= rc.N - 1;
   if (!whole) {
-    const CellGrid cg = cell_grid(bb + (size_t)gi * 6, N, 0.f);
+    const CellGrid cg = cell_grid(bb + (size_t)rc.gi * 6, rc.N, 0.f);
     const int g = cg.g;
+    const CellTable ct{cell_start, rc.g0 + rc.gi, n_total + n_graphs - 1, g};
     const int c0 = __builtin_amdgcn_readfirstlane(cell_of(xi0, cg.lo[0], cg.inv_w[0], g));
     const int c1 = __builtin_amdgcn_readfirstlane(cell_of(xi1, cg.lo[1], cg.inv_w[1], g));
     const int c2 = __builtin_amdgcn_readfirstlane(cell_of(xi2, cg.lo[2], cg.inv_w[2], g));
@@ -390,18 +399,15 @@ __global__ __launch_bounds__(256) void neighbor_select_knn_cells_kernel(
       if (box_covers_grid(b1, g)) break;
       int cnt = 0;
       for (int u = lane; u < box_runs(b1); u += 64) {
-        const CellSeg sg = box_run(b1, u, g);
-        cnt += cell_start[imin(tab + sg.c1, last) + 1] - cell_start[imin(tab + sg.c0, last)];
+        int p, e;
+        ct.cells(box_run(b1, u, g), p, e);
+        cnt += e - p;
       }
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
       if (__builtin_amdgcn_readfirstlane(cnt) - 1 >= kk) break;
     }
-    walk_segments(best, box_runs(b1), [&](int u, int& p, int& e) {
-      const CellSeg sg = box_run(b1, u, g);
-      p = cell_start[imin(tab + sg.c0, last)];
-      e = cell_start[imin(tab + sg.c1, last) + 1];
-    }, n_total, kk, lane, i, g0, r2_max, xi0, xi1, xi2, sorted);
+    ct.walk_box(best, b1, rc, n_total, lane, r2_max, sorted);
     // phase 2: what the cut-off search with r2 = D walks outside the shell box
     const u64 kth = shfl64(best, kk - 1);
     const float D = kth != KEY_NONE ? __uint_as_float((unsigned)(kth >> 32)) : r2_max;
@@ -410,31 +416,19 @@ __global__ __launch_bounds__(256) void neighbor_select_knn_cells_kernel(
       whole = true;
     } else {
       const CellBox b2 = uniform_box(cell_box(cg, xi0, xi1, xi2, rr));
-      if (!box_inside(b2, b1)) {
-#if NONODE_KNN_REWALK
-        best = KEY_NONE;
-        walk_segments(best, box_runs(b2), [&](int u, int& p, int& e) {
-          const CellSeg sg = box_run(b2, u, g);
-          p = cell_start[imin(tab + sg.c0, last)];
-          e = cell_start[imin(tab + sg.c1, last) + 1];
-        }, n_total, kk, lane, i, g0, r2_max, xi0, xi1, xi2, sorted);
-#else
+      if (!box_inside(b2, b1))
         walk_segments(best, 2 * box_runs(b2), [&](int u, int& p, int& e) {
           const CellSeg sg = box_run_outside(b2, b1, u >> 1, u & 1, g);
-          if (sg.c0 > sg.c1) return;
-          p = cell_start[imin(tab + sg.c0, last)];
-          e = cell_start[imin(tab + sg.c1, last) + 1];
-        }, n_total, kk, lane, i, g0, r2_max, xi0, xi1, xi2, sorted);
-#endif
-      }
+          if (sg.c0 <= sg.c1) ct.cells(sg, p, e);
+        }, rc, n_total, lane, r2_max, sorted);
     }
   }
   if (whole) {   // the brute-force search on the graph's run of the sorted order, its non-finite bucket included
     best = KEY_NONE;
-    walk_segments(best, 1, [&](int, int& p, int& e) { p = g0; e = g0 + N; }, n_total, kk, lane, i, g0, r2_max, xi0,
-                  xi1, xi2, sorted);
+    walk_segments(best, 1, [&](int, int& p, int& e) { p = rc.g0; e = rc.g0 + rc.N; }, rc, n_total, lane, r2_max,
+                  sorted);
   }
-  topk_write(best, kk, lane, r, g0, pitch, tmp, deg);
+  topk_write(best, kk, lane, rc.r, rc.g0, pitch, tmp, deg);
 }
 
 // thread t = r pitch + l of the n_total pitch fixed-pitch slots: entry l of row r moves to row_ptr[r] + l;
@@ -588,81 +582,87 @@ __global__ __launch_bounds__(256) void sender_sort_kernel(int n_total, const int
 
 long long neighbor_capacity(int B, int N, int k) { return (long long)B * N * (k < N - 1 ? k : N - 1); }
 
-// The builder's launches for a batch over n_total rows whose largest graph has n_max: the workspace rows
-// at the fixed pitch min(k, n_max - 1), the outputs with cap entries. graph_of null: equal sizes, every
-// graph n_max rows (cap = n_total pitch); otherwise the n_graphs graphs graph_ptr / graph_of name.
-int launch_neighbor_graph(const char* who, int n_total, int n_max, int k, long long cap, float r2_max, int n_graphs,
-                          const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col, int* eid,
-                          int* rows, void* workspace, hipStream_t s) {
-  const int pitch = k < n_max - 1 ? k : n_max - 1;
-  int* deg = (int*)workspace;
-  int* tmp = deg + n_total;
-  if (pitch == 0) {   // graphs of one node: no pair at all
-    if (hipMemsetAsync(row_ptr, 0, ((size_t)n_total + 1) * sizeof(int), s) != hipSuccess)
-      return fail(NONODE_ELAUNCH, "%s: memset", who);
-    return NONODE_OK;
-  }
-  hipLaunchKernelGGL(neighbor_select_kernel, dim3((n_total + 3) / 4), dim3(256), 0, s, n_total, n_max, k, pitch, r2_max,
-                     n_graphs, graph_ptr, graph_of, x, tmp, deg);
-  if (int rc = check_launch("neighbor_select_kernel")) return rc;
-  if (int rc = nonode_tu::graph_scan(n_total, deg, row_ptr, s)) return rc;
-  const long long slots = (long long)n_total * pitch;
-  hipLaunchKernelGGL(neighbor_compact_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, cap, n_total,
-                     pitch, row_ptr, tmp, col, eid, rows);
-  return check_launch("neighbor_compact_kernel");
-}
-
-// The cell-list builder's workspace, in ints: sorted (4 n_total, first: 16-byte rows), deg, tmp (as above),
-// bucket (n_total), then bb (6 G) and cnt (n_total + G) side by side (one memset), cell_start (n_total + G + 1).
+// The cell-list builder's workspace, in ints: sorted (4 n_total, first: 16-byte rows), deg, tmp (as the brute-force
+// builder's), bucket (n_total), then bb (6 G) and cnt (n_total + G) side by side (one memset), cell_start
+// (n_total + G + 1).
 size_t cells_workspace_ints(int G, int n_total, int pitch) {
   return (size_t)n_total * (8 + (size_t)pitch) + 8 * (size_t)G + 1;
 }
 
-// The cell-list builder's launches (finite r2_max): memset, bounding boxes, cell counts, scan, fill, the
-// search, then the brute-force builder's own scan and compaction. Every grid is a function of n_total and the
-// pitch; nothing is read back. knn: the k-NN search on the same list (any r2_max): the grid of rr = 0 and
-// neighbor_select_knn_cells_kernel in place of the cut-off's radius and search.
-int launch_neighbor_graph_cells(bool knn, int n_total, int n_max, int k, long long cap, float r2_max, int n_graphs,
-                                const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
-                                int* eid, int* rows, void* workspace, hipStream_t s) {
-  const char* who = knn ? "neighbor_graph_knn_cells" : "neighbor_graph_cells";
+// The builder's launches for a batch over n_total rows whose largest graph has n_max: the workspace rows
+// at the fixed pitch min(k, n_max - 1), the outputs with cap entries. graph_of null: equal sizes, every
+// graph n_max rows (cap = n_total pitch); otherwise the n_graphs graphs graph_ptr / graph_of name.
+// CELLS (finite r2_max) / KNN_CELLS (any r2_max; the grid of rr = 0) build the cell list before their search. Every
+// grid is a function of n_total and the pitch; nothing is read back.
+enum Search { BRUTE, CELLS, KNN_CELLS };
+int launch_neighbor_graph(Search how, const char* who, int n_total, int n_max, int k, long long cap, float r2_max,
+                          int n_graphs, const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr,
+                          int* col, int* eid, int* rows, void* workspace, hipStream_t s) {
   const int pitch = k < n_max - 1 ? k : n_max - 1;
   if (pitch == 0) {   // graphs of one node: no pair at all
     if (hipMemsetAsync(row_ptr, 0, ((size_t)n_total + 1) * sizeof(int), s) != hipSuccess)
       return fail(NONODE_ELAUNCH, "%s: memset", who);
     return NONODE_OK;
   }
-  f4* sorted = (f4*)workspace;
-  int* deg = (int*)workspace + 4 * (size_t)n_total;
-  int* tmp = deg + n_total;
-  int* bucket = tmp + (size_t)n_total * pitch;
-  unsigned* bb = (unsigned*)(bucket + n_total);
-  int* cnt = (int*)(bb + 6 * (size_t)n_graphs);
-  int* cell_start = cnt + n_total + n_graphs;
-  const float rr = knn ? 0.f : cell_rr(r2_max);
-  if (hipMemsetAsync(bb, 0, (6 * (size_t)n_graphs + (size_t)n_total + n_graphs) * sizeof(int), s) != hipSuccess)
-    return fail(NONODE_ELAUNCH, "%s: memset", who);
   const dim3 per_node((n_total + 255) / 256), per_wave((n_total + 3) / 4);
-  hipLaunchKernelGGL(cell_bbox_kernel, per_node, dim3(256), 0, s, n_total, n_max, n_graphs, graph_ptr, graph_of, x, bb);
-  if (int rc = check_launch("cell_bbox_kernel")) return rc;
-  hipLaunchKernelGGL(cell_count_kernel, per_node, dim3(256), 0, s, n_total, n_max, n_graphs, rr, graph_ptr, graph_of,
-                     x, bb, cnt, bucket);
-  if (int rc = check_launch("cell_count_kernel")) return rc;
-  if (int rc = nonode_tu::graph_scan(n_total + n_graphs, cnt, cell_start, s)) return rc;
-  hipLaunchKernelGGL(cell_fill_kernel, per_node, dim3(256), 0, s, n_total, x, bucket, cnt, sorted);
-  if (int rc = check_launch("cell_fill_kernel")) return rc;
-  if (knn)
-    hipLaunchKernelGGL(neighbor_select_knn_cells_kernel, per_wave, dim3(256), 0, s, n_total, n_max, k, pitch, r2_max,
-                       n_graphs, graph_ptr, graph_of, sorted, cell_start, bb, tmp, deg);
-  else
-    hipLaunchKernelGGL(neighbor_select_cells_kernel, per_wave, dim3(256), 0, s, n_total, n_max, k, pitch, r2_max, rr,
-                       n_graphs, graph_ptr, graph_of, sorted, cell_start, bb, tmp, deg);
-  if (int rc = check_launch(knn ? "neighbor_select_knn_cells_kernel" : "neighbor_select_cells_kernel")) return rc;
+  int* deg = (int*)workspace + (how == BRUTE ? 0 : 4 * (size_t)n_total);
+  int* tmp = deg + n_total;
+  if (how == BRUTE) {
+    hipLaunchKernelGGL(neighbor_select_kernel, per_wave, dim3(256), 0, s, n_total, n_max, k, pitch, r2_max, n_graphs,
+                       graph_ptr, graph_of, x, tmp, deg);
+    if (int rc = check_launch("neighbor_select_kernel")) return rc;
+  } else {
+    f4* sorted = (f4*)workspace;
+    int* bucket = tmp + (size_t)n_total * pitch;
+    unsigned* bb = (unsigned*)(bucket + n_total);
+    int* cnt = (int*)(bb + 6 * (size_t)n_graphs);
+    int* cell_start = cnt + n_total + n_graphs;
+    const float rr = how == KNN_CELLS ? 0.f : cell_rr(r2_max);
+    if (hipMemsetAsync(bb, 0, (6 * (size_t)n_graphs + (size_t)n_total + n_graphs) * sizeof(int), s) != hipSuccess)
+      return fail(NONODE_ELAUNCH, "%s: memset", who);
+    hipLaunchKernelGGL(cell_bbox_kernel, per_node, dim3(256), 0, s, n_total, n_max, n_graphs, graph_ptr, graph_of, x,
+                       bb);
+    if (int rc = check_launch("cell_bbox_kernel")) return rc;
+    hipLaunchKernelGGL(cell_count_kernel, per_node, dim3(256), 0, s, n_total, n_max, n_graphs, rr, graph_ptr, graph_of,
+                       x, bb, cnt, bucket);
+    if (int rc = check_launch("cell_count_kernel")) return rc;
+    if (int rc = nonode_tu::graph_scan(n_total + n_graphs, cnt, cell_start, s)) return rc;
+    hipLaunchKernelGGL(cell_fill_kernel, per_node, dim3(256), 0, s, n_total, x, bucket, cnt, sorted);
+    if (int rc = check_launch("cell_fill_kernel")) return rc;
+    if (how == KNN_CELLS)
+      hipLaunchKernelGGL(neighbor_select_knn_cells_kernel, per_wave, dim3(256), 0, s, n_total, n_max, k, pitch, r2_max,
+                         n_graphs, graph_ptr, graph_of, sorted, cell_start, bb, tmp, deg);
+    else
+      hipLaunchKernelGGL(neighbor_select_cells_kernel, per_wave, dim3(256), 0, s, n_total, n_max, k, pitch, r2_max, rr,
+                         n_graphs, graph_ptr, graph_of, sorted, cell_start, bb, tmp, deg);
+    if (int rc = check_launch(how == KNN_CELLS ? "neighbor_select_knn_cells_kernel" : "neighbor_select_cells_kernel"))
+      return rc;
+  }
   if (int rc = nonode_tu::graph_scan(n_total, deg, row_ptr, s)) return rc;
   const long long slots = (long long)n_total * pitch;
   hipLaunchKernelGGL(neighbor_compact_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, cap, n_total,
                      pitch, row_ptr, tmp, col, eid, rows);
   return check_launch("neighbor_compact_kernel");
+}
+
+// The host diagnostics' graph gi: its rows and its grid at radius rr, through the functions the kernels run.
+struct HostGraph {
+  GraphRows rows;
+  CellGrid cg;
+};
+HostGraph host_graph(const int* graph_ptr, int gi, int n_max, int n_total, const float* x, float rr) {
+  const GraphRows rows = graph_rows(graph_ptr, gi, n_max, n_total);
+  unsigned bb[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+  for (int r = rows.r0; r < rows.r0 + rows.n; ++r) {
+    const float* p = x + (size_t)r * 3;
+    if (!cell_finite(p[0], p[1], p[2])) continue;
+    for (int a = 0; a < 3; ++a) {
+      const unsigned key = cell_key(p[a]);
+      if (~key > bb[a]) bb[a] = ~key;
+      if (key > bb[3 + a]) bb[3 + a] = key;
+    }
+  }
+  return HostGraph{rows, cell_grid(bb, rows.n, rr)};
 }
 
 int launch_node_features(int n_graphs, int n_total, int n_each, int F, const int* graph_ptr, const float* loc,
@@ -695,8 +695,8 @@ int nonode_neighbor_graph(int B, int N, int k, float r2_max, const float* x, int
   if (workspace_bytes < nonode_neighbor_graph_workspace_bytes(B, N, k))
     return fail(NONODE_EINVAL, "neighbor_graph: workspace %zu < %zu", workspace_bytes,
                 nonode_neighbor_graph_workspace_bytes(B, N, k));
-  return launch_neighbor_graph("neighbor_graph", B * N, N, k, cap, r2_max, B, nullptr, nullptr, x, row_ptr, col, eid,
-                               rows, workspace, (hipStream_t)stream);
+  return launch_neighbor_graph(BRUTE, "neighbor_graph", B * N, N, k, cap, r2_max, B, nullptr, nullptr, x, row_ptr, col,
+                               eid, rows, workspace, (hipStream_t)stream);
 }
 
 size_t nonode_neighbor_graph_ragged_workspace_bytes(int n_total, int n_max, int k) {
@@ -705,70 +705,62 @@ size_t nonode_neighbor_graph_ragged_workspace_bytes(int n_total, int n_max, int 
   return ((size_t)n_total + (size_t)n_total * (k < n_max - 1 ? k : n_max - 1)) * sizeof(int);
 }
 
-int nonode_neighbor_graph_ragged(int G, int n_total, int n_max, int k, long long cap, float r2_max,
-                                 const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
-                                 int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream) {
-  if (G < 1 || n_total < G || n_total >= (1 << 30) || n_max < 1 || n_max > n_total || k < 1 || k > 64 ||
-      !(r2_max > 0.f) || cap < 0 || cap >= (1ll << 31) ||
-      cap > (long long)n_total * (k < n_max - 1 ? k : n_max - 1))
-    return fail(NONODE_EINVAL, "neighbor_graph_ragged: G=%d n_total=%d n_max=%d k=%d cap=%lld r2_max=%g (k in [1, 64], "
-                "r2_max > 0, cap <= n_total min(k, n_max - 1))", G, n_total, n_max, k, cap, (double)r2_max);
-  if (!graph_ptr || !graph_of || !x || !row_ptr || !workspace || (cap > 0 && (!col || !eid || !rows)))
-    return fail(NONODE_EINVAL, "neighbor_graph_ragged: null pointer");
-  if (workspace_bytes < nonode_neighbor_graph_ragged_workspace_bytes(n_total, n_max, k))
-    return fail(NONODE_EINVAL, "neighbor_graph_ragged: workspace %zu < %zu", workspace_bytes,
-                nonode_neighbor_graph_ragged_workspace_bytes(n_total, n_max, k));
-  return launch_neighbor_graph("neighbor_graph_ragged", n_total, n_max, k, cap, r2_max, G, graph_ptr, graph_of, x,
-                               row_ptr, col, eid, rows, workspace, (hipStream_t)stream);
-}
-
 size_t nonode_neighbor_graph_cells_workspace_bytes(int G, int n_total, int n_max, int k) {
   if (G < 1 || n_total < G || n_total >= (1 << 30) || n_max <= 0 || n_max > n_total || k < 1 || k > 64) return 0;
   return cells_workspace_ints(G, n_total, k < n_max - 1 ? k : n_max - 1) * sizeof(int);
-}
-
-// the host checks and the launches of both searches on the cell list (knn: r2_max may be +inf)
-static int neighbor_graph_cells_entry(bool knn, int G, int n_total, int n_max, int k, long long cap, float r2_max,
-                                      const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
-                                      int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* who = knn ? "neighbor_graph_knn_cells" : "neighbor_graph_cells";
-  if (G < 1 || n_total < G || n_total >= (1 << 30) || n_max < 1 || n_max > n_total || k < 1 || k > 64 ||
-      !(r2_max > 0.f) || (!knn && !cell_finite(r2_max)) || cap < 0 || cap >= (1ll << 31) ||
-      cap > (long long)n_total * (k < n_max - 1 ? k : n_max - 1))
-    return fail(NONODE_EINVAL, "%s: G=%d n_total=%d n_max=%d k=%d cap=%lld r2_max=%g (k in [1, 64], r2_max > 0%s, "
-                "cap <= n_total min(k, n_max - 1))", who, G, n_total, n_max, k, cap, (double)r2_max,
-                knn ? "" : " and finite");
-  if ((graph_ptr == nullptr) != (graph_of == nullptr))
-    return fail(NONODE_EINVAL, "%s: graph_ptr and graph_of go together (both null: equal sizes)", who);
-  if (!graph_of && (long long)G * n_max != n_total)
-    return fail(NONODE_EINVAL, "%s: equal sizes need n_total = G n_max, got G=%d n_max=%d n_total=%d", who, G, n_max,
-                n_total);
-  if (!x || !row_ptr || !workspace || (cap > 0 && (!col || !eid || !rows)))
-    return fail(NONODE_EINVAL, "%s: null pointer", who);
-  if (((size_t)workspace & 15) != 0) return fail(NONODE_EINVAL, "%s: workspace not 16-byte aligned", who);
-  if (workspace_bytes < nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k))
-    return fail(NONODE_EINVAL, "%s: workspace %zu < %zu", who, workspace_bytes,
-                nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k));
-  return launch_neighbor_graph_cells(knn, n_total, n_max, k, cap, r2_max, G, graph_ptr, graph_of, x, row_ptr, col, eid,
-                                     rows, workspace, (hipStream_t)stream);
-}
-
-int nonode_neighbor_graph_cells(int G, int n_total, int n_max, int k, long long cap, float r2_max,
-                                const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
-                                int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream) {
-  return neighbor_graph_cells_entry(false, G, n_total, n_max, k, cap, r2_max, graph_ptr, graph_of, x, row_ptr, col, eid,
-                                    rows, workspace, workspace_bytes, stream);
 }
 
 size_t nonode_neighbor_graph_knn_cells_workspace_bytes(int G, int n_total, int n_max, int k) {
   return nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k);   // the same list, the same rows
 }
 
+// The host checks and the launches of the entries that take (G, ..., descriptors). CELLS wants a finite r2_max; both
+// cell searches take null descriptors for equal sizes (n_total = G n_max) and a 16-byte aligned workspace.
+static int neighbor_graph_entry(Search how, const char* who, int G, int n_total, int n_max, int k, long long cap,
+                                float r2_max, const int* graph_ptr, const int* graph_of, const float* x,
+                                int* row_ptr, int* col, int* eid, int* rows, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+  const bool finite = how == CELLS, cells = how != BRUTE;
+  const size_t need = cells ? nonode_neighbor_graph_cells_workspace_bytes(G, n_total, n_max, k)
+                            : nonode_neighbor_graph_ragged_workspace_bytes(n_total, n_max, k);
+  if (G < 1 || n_total < G || n_total >= (1 << 30) || n_max < 1 || n_max > n_total || k < 1 || k > 64 ||
+      !(r2_max > 0.f) || (finite && !cell_finite(r2_max)) || cap < 0 || cap >= (1ll << 31) ||
+      cap > (long long)n_total * (k < n_max - 1 ? k : n_max - 1))
+    return fail(NONODE_EINVAL, "%s: G=%d n_total=%d n_max=%d k=%d cap=%lld r2_max=%g (k in [1, 64], r2_max > 0%s, "
+                "cap <= n_total min(k, n_max - 1))", who, G, n_total, n_max, k, cap, (double)r2_max,
+                finite ? " and finite" : "");
+  if (cells && (graph_ptr == nullptr) != (graph_of == nullptr))
+    return fail(NONODE_EINVAL, "%s: graph_ptr and graph_of go together (both null: equal sizes)", who);
+  if (cells && !graph_of && (long long)G * n_max != n_total)
+    return fail(NONODE_EINVAL, "%s: equal sizes need n_total = G n_max, got G=%d n_max=%d n_total=%d", who, G, n_max,
+                n_total);
+  if ((!cells && (!graph_ptr || !graph_of)) || !x || !row_ptr || !workspace || (cap > 0 && (!col || !eid || !rows)))
+    return fail(NONODE_EINVAL, "%s: null pointer", who);
+  if (cells && ((size_t)workspace & 15) != 0) return fail(NONODE_EINVAL, "%s: workspace not 16-byte aligned", who);
+  if (workspace_bytes < need) return fail(NONODE_EINVAL, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+  return launch_neighbor_graph(how, who, n_total, n_max, k, cap, r2_max, G, graph_ptr, graph_of, x, row_ptr, col, eid,
+                               rows, workspace, (hipStream_t)stream);
+}
+
+int nonode_neighbor_graph_ragged(int G, int n_total, int n_max, int k, long long cap, float r2_max,
+                                 const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
+                                 int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream) {
+  return neighbor_graph_entry(BRUTE, "neighbor_graph_ragged", G, n_total, n_max, k, cap, r2_max, graph_ptr, graph_of, x,
+                              row_ptr, col, eid, rows, workspace, workspace_bytes, stream);
+}
+
+int nonode_neighbor_graph_cells(int G, int n_total, int n_max, int k, long long cap, float r2_max,
+                                const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
+                                int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream) {
+  return neighbor_graph_entry(CELLS, "neighbor_graph_cells", G, n_total, n_max, k, cap, r2_max, graph_ptr, graph_of, x,
+                              row_ptr, col, eid, rows, workspace, workspace_bytes, stream);
+}
+
 int nonode_neighbor_graph_knn_cells(int G, int n_total, int n_max, int k, long long cap, float r2_max,
                                     const int* graph_ptr, const int* graph_of, const float* x, int* row_ptr, int* col,
                                     int* eid, int* rows, void* workspace, size_t workspace_bytes, void* stream) {
-  return neighbor_graph_cells_entry(true, G, n_total, n_max, k, cap, r2_max, graph_ptr, graph_of, x, row_ptr, col, eid,
-                                    rows, workspace, workspace_bytes, stream);
+  return neighbor_graph_entry(KNN_CELLS, "neighbor_graph_knn_cells", G, n_total, n_max, k, cap, r2_max, graph_ptr,
+                              graph_of, x, row_ptr, col, eid, rows, workspace, workspace_bytes, stream);
 }
 
 // Diagnostic (host arrays, no GPU): the grid, the binning and the search boxes of the cell-list search, from
@@ -782,23 +774,9 @@ int nonode_debug_neighbor_cells(int G, int n_total, int n_max, float r2_max, con
   const float rr = cell_rr(r2_max);
   if (rr_out) *rr_out = rr;
   for (int gi = 0; gi < G; ++gi) {
-    int g0 = gi * n_max, n = n_max;
-    if (graph_ptr) {   // (graph_rows, on the host)
-      const int lo = imin(imax(graph_ptr[gi], 0), n_total), hi = imin(imax(graph_ptr[gi + 1], 0), n_total);
-      g0 = lo;
-      n = hi - lo;
-    }
-    unsigned bb[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-    for (int r = g0; r < g0 + n; ++r) {
-      const float* p = x + (size_t)r * 3;
-      if (!cell_finite(p[0], p[1], p[2])) continue;
-      for (int a = 0; a < 3; ++a) {
-        const unsigned key = cell_key(p[a]);
-        if (~key > bb[a]) bb[a] = ~key;
-        if (key > bb[3 + a]) bb[3 + a] = key;
-      }
-    }
-    const CellGrid cg = cell_grid(bb, n, rr);
+    const HostGraph hg = host_graph(graph_ptr, gi, n_max, n_total, x, rr);
+    const int g0 = hg.rows.r0, n = hg.rows.n;
+    const CellGrid& cg = hg.cg;
     if (grid) grid[gi] = cg.g;
     if (box)
       for (int a = 0; a < 3; ++a) {
@@ -833,23 +811,10 @@ int nonode_debug_neighbor_knn_cells(int G, int n_total, int n_max, int k, float 
                 k, (double)r2_max);
   const int pitch = k < n_max - 1 ? k : n_max - 1;
   for (int gi = 0; gi < G; ++gi) {
-    int g0 = gi * n_max, n = n_max;
-    if (graph_ptr) {   // (graph_rows, on the host)
-      const int lo = imin(imax(graph_ptr[gi], 0), n_total), hi = imin(imax(graph_ptr[gi + 1], 0), n_total);
-      g0 = lo;
-      n = hi - lo;
-    }
+    const HostGraph hg = host_graph(graph_ptr, gi, n_max, n_total, x, 0.f);
+    const int g0 = hg.rows.r0, n = hg.rows.n;
     const float* xg = x + (size_t)g0 * 3;
-    unsigned bb[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-    for (int j = 0; j < n; ++j) {
-      if (!cell_finite(xg[j * 3], xg[j * 3 + 1], xg[j * 3 + 2])) continue;
-      for (int a = 0; a < 3; ++a) {
-        const unsigned key = cell_key(xg[j * 3 + a]);
-        if (~key > bb[a]) bb[a] = ~key;
-        if (key > bb[3 + a]) bb[3 + a] = key;
-      }
-    }
-    const CellGrid cg = cell_grid(bb, n, 0.f);
+    const CellGrid& cg = hg.cg;
     const int g = cg.g, nc = g * g * g;
     // the graph's part of the sorted order: its nodes by cell (the order inside a cell does not matter), the
     // non-finite ones in the trailing bucket nc; start = its part of cell_start
@@ -880,7 +845,8 @@ int nonode_debug_neighbor_knn_cells(int G, int n_total, int n_max, int k, float 
           const int j = order[p];
           const float d2 = dist2(xi0, xi1, xi2, xg[j * 3], xg[j * 3 + 1], xg[j * 3 + 2]);
           ++st[13];
-          if (j != i && d2 <= r2_max) keys.push_back(((u64)__builtin_bit_cast(unsigned, d2) << 32) | (unsigned)j);
+          const u64 key = candidate_key(d2, j, i, r2_max);
+          if (key != KEY_NONE) keys.push_back(key);
         }
       };
       if (kk > 0) {

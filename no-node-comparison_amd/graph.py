@@ -520,26 +520,19 @@ def _build_neighbor_graph(x, k, r2, by_sender, B, N, batch, method="brute"):
     col, eid, rows = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
     L = _lib.lib()
     out = (_lib.ptr(row_ptr), _lib.ptr(col), _lib.ptr(eid), _lib.ptr(rows))
+    G, n_max = (B, N) if batch is None else (batch.n_graphs, batch.n_max)
+    desc = (None, None) if batch is None else (batch.graph_ptr, batch.graph_of)
+    described = (G, n_total, n_max, k, cap, r2, _lib.ptr(desc[0]), _lib.ptr(desc[1]))
+    # the entry, what its workspace query takes, its arguments before x
     if method in ("cells", "knn_cells"):
-        G, n_max = (B, N) if batch is None else (batch.n_graphs, batch.n_max)
-        desc = (None, None) if batch is None else (batch.graph_ptr, batch.graph_of)
-        query, build = ((L.nonode_neighbor_graph_cells_workspace_bytes, L.nonode_neighbor_graph_cells)
-                        if method == "cells" else
-                        (L.nonode_neighbor_graph_knn_cells_workspace_bytes, L.nonode_neighbor_graph_knn_cells))
-        ws_bytes = query(G, n_total, n_max, k)
-        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
-        _lib.check(build(G, n_total, n_max, k, cap, r2, _lib.ptr(desc[0]), _lib.ptr(desc[1]), _lib.ptr(x), *out,
-                         _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
+        name, sizes, lead = "nonode_neighbor_graph_" + method, (G, n_total, n_max, k), described
     elif batch is None:
-        ws_bytes = L.nonode_neighbor_graph_workspace_bytes(B, N, k)
-        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
-        _lib.check(L.nonode_neighbor_graph(B, N, k, r2, _lib.ptr(x), *out, _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
+        name, sizes, lead = "nonode_neighbor_graph", (B, N, k), (B, N, k, r2)
     else:
-        ws_bytes = L.nonode_neighbor_graph_ragged_workspace_bytes(n_total, batch.n_max, k)
-        ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
-        _lib.check(L.nonode_neighbor_graph_ragged(batch.n_graphs, n_total, batch.n_max, k, cap, r2,
-                                                  _lib.ptr(batch.graph_ptr), _lib.ptr(batch.graph_of), _lib.ptr(x),
-                                                  *out, _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
+        name, sizes, lead = "nonode_neighbor_graph_ragged", (n_total, n_max, k), described
+    ws_bytes = getattr(L, name + "_workspace_bytes")(*sizes)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+    _lib.check(getattr(L, name)(*lead, _lib.ptr(x), *out, _lib.ptr(ws), ws_bytes, _lib.stream_of(x)))
     n_nodes = N if batch is None else None
     if not by_sender:
         return NeighborGraph(rows, col, row_ptr, eid, n_nodes, batch=batch)

@@ -13,17 +13,12 @@ import torch
 
 import no_node_comparison_amd as pkg
 from no_node_comparison_amd import graph, harness
+from tests._neighbor_gpu import DEV, NAMES, assert_ref as _assert_ref, dev as _dev, same_graph as _same_graph
 from tests._neighbor_ref import cutoff_straddlers, d2_unfused, neighbor_ref, tied_pairs
 from tests._ragged_ref import ragged_neighbor_ref
 from tests.conftest import load_golden, params_of
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-NAMES = ("row_ptr", "col", "rows", "eid")
-
-
-def _dev(a):
-    return torch.tensor(np.ascontiguousarray(a)).to(DEV)
 
 
 def _points(n, seed, scale=1.5):
@@ -36,22 +31,6 @@ def _both(x, B, N, k, r_cut, **kw):
     b = graph.neighbor_graph(xd, B, N, k, r_cut, method="cells", **kw)
     torch.cuda.synchronize()
     return a, b
-
-
-def _same_graph(a, b, sender=False):
-    for n in NAMES + (("srow_ptr", "seid", "valid") if sender else ()):
-        assert torch.equal(getattr(a, n), getattr(b, n)), n
-    assert a.capacity == b.capacity and a.n_nodes == b.n_nodes
-
-
-def _assert_ref(ng, ref):
-    got = {n: getattr(ng, n).cpu().numpy() for n in NAMES}
-    E = int(got["row_ptr"][-1])
-    assert ng.capacity == ref["cap"] and E == ref["E"]
-    for n in NAMES:
-        assert got[n].dtype == np.int32 and got[n].shape == ref[n].shape, n
-        assert np.array_equal(got[n], ref[n]), n
-    assert np.all(got["col"][E:] == -1) and np.all(got["rows"][E:] == -1)
 
 
 def _check(x, B, N, k, r_cut):

@@ -14,30 +14,11 @@ import torch
 import no_node_comparison_amd as pkg
 from no_node_comparison_amd import graph, harness
 from tests._knn_cells_cases import FAMILIES, RAGGED, cases, points
+from tests._neighbor_gpu import DEV, assert_ref as _assert_ref, dev as _dev, same_graph as _same_graph
 from tests._neighbor_ref import cutoff_straddlers, neighbor_ref, tied_pairs
 from tests.conftest import load_golden, params_of
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-NAMES = ("row_ptr", "col", "rows", "eid")
-SENDER = ("srow_ptr", "seid", "valid")
-
-
-def _dev(a):
-    return torch.tensor(np.ascontiguousarray(a)).to(DEV)
-
-
-def _same_graph(a, b, sender=False):
-    for n in NAMES + (SENDER if sender else ()):
-        assert torch.equal(getattr(a, n), getattr(b, n)), n
-    assert a.capacity == b.capacity and a.n_nodes == b.n_nodes
-
-
-def _assert_ref(ng, ref):
-    got = {n: getattr(ng, n).cpu().numpy() for n in NAMES}
-    assert ng.capacity == ref["cap"] and int(got["row_ptr"][-1]) == ref["E"]
-    for n in NAMES:
-        assert got[n].dtype == np.int32 and np.array_equal(got[n], ref[n]), n
 
 
 # ---- 1. bitwise the brute-force builder's arrays ---------------------------------------------------------------
