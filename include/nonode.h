@@ -477,17 +477,45 @@ int nonode_segno_rollout(int B, int N, int in_node, int n_edge_feat, int traj_le
  * loc0, vel0 [S][3][N] the initial state after the reference's velocity normalisation and wall
  * clamp; charges [S][N]; Coulomb forces strength q_i q_j (x_i - x_j) / |x_i - x_j|^3 clamped to
  * +-max_F per component; leapfrog with step dt. Outputs loc_out, vel_out [S][T/sample_freq - 1][3][N]
- * (the reference's samples at steps sample_freq, 2 sample_freq, ...). N <= 1024. */
+ * (the reference's samples at steps sample_freq, 2 sample_freq, ...). N <= 1024 (one workgroup holds a
+ * trajectory); nonode_sim_charged_tiled takes larger N. */
 int nonode_sim_charged(int S, int N, int T, int sample_freq, double dt, double max_F, double strength,
                        const double* loc0, const double* vel0, const double* charges, double* loc_out,
                        double* vel_out, void* stream);
 
 /* GravitySim.sample_trajectory_batch (synthetic_sim.py:407-481): pos0, vel0 [S][N][3] (centre-of-mass
  * velocity already removed), mass [S][N]; softened gravity, kick-drift-kick with step dt. Outputs
- * pos_out, vel_out, force_out (= a m) [S][T/sample_freq][N][3] sampled at steps 0, sample_freq, ... */
+ * pos_out, vel_out, force_out (= a m) [S][T/sample_freq][N][3] sampled at steps 0, sample_freq, ...
+ * N <= 1024 (one workgroup holds a trajectory); nonode_sim_gravity_tiled takes larger N. */
 int nonode_sim_gravity(int S, int N, int T, int sample_freq, double dt, double G, double softening,
                        const double* pos0, const double* vel0, const double* mass, double* pos_out,
                        double* vel_out, double* force_out, void* stream);
+
+/* The tiled simulators: the same trajectories for any N up to 2^20 with S N < 2^31, one launch per time
+ * step (a workgroup owns a tile of receivers and stages the trajectory's senders through LDS in chunks;
+ * every force sum runs over j = 0 .. N-1 in ascending order, so at N <= 1024 the outputs equal the
+ * entries' above bit for bit). nonode_sim_tiled_shape reports the tile: receivers per workgroup and
+ * senders per LDS chunk. */
+int nonode_sim_tiled_shape(int* receivers, int* senders);
+
+/* Bytes of workspace for the two entries below: 9 S N doubles (two position buffers [3][S N] and the
+ * velocities [S N][3]). Host only; 0 for sizes the entries refuse (S < 1, N < 1, N > 2^20, S N >= 2^31). */
+size_t nonode_sim_tiled_workspace_bytes(int S, int N);
+
+/* GravitySim.sample_trajectory_batch (synthetic_sim.py:407-481) as nonode_sim_gravity computes it, same
+ * layouts and sampling; N in [1, 2^20]. workspace: device memory, 8-byte aligned, at least
+ * nonode_sim_tiled_workspace_bytes(S, N). Bad sizes, T % sample_freq != 0, a null pointer or a short
+ * workspace return NONODE_EINVAL before any device work. */
+int nonode_sim_gravity_tiled(int S, int N, int T, int sample_freq, double dt, double G, double softening,
+                             const double* pos0, const double* vel0, const double* mass, double* pos_out,
+                             double* vel_out, double* force_out, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
+/* ChargedParticlesSim.sample_trajectory (synthetic_sim.py:220-296) as nonode_sim_charged computes it, same
+ * layouts and sampling; N in [2, 2^20]. workspace and refusals as nonode_sim_gravity_tiled. */
+int nonode_sim_charged_tiled(int S, int N, int T, int sample_freq, double dt, double max_F, double strength,
+                             const double* loc0, const double* vel0, const double* charges, double* loc_out,
+                             double* vel_out, void* workspace, size_t workspace_bytes, void* stream);
 
 
 /* ---- dataset -> device batches ---- */

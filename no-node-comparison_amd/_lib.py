@@ -50,6 +50,8 @@ SYMBOLS = (
     "nonode_neighbor_graph_cells_workspace_bytes", "nonode_neighbor_graph_cells", "nonode_debug_neighbor_cells",
     "nonode_neighbor_graph_knn_cells_workspace_bytes", "nonode_neighbor_graph_knn_cells",
     "nonode_debug_neighbor_knn_cells",
+    "nonode_sim_tiled_shape", "nonode_sim_tiled_workspace_bytes", "nonode_sim_gravity_tiled",
+    "nonode_sim_charged_tiled",
 )
 
 VARIANT_EGNO = 0
@@ -223,6 +225,11 @@ def lib():
     _d = ctypes.c_double
     L.nonode_sim_charged.argtypes = [_i] * 4 + [_d] * 3 + [_vp] * 6
     L.nonode_sim_gravity.argtypes = [_i] * 4 + [_d] * 3 + [_vp] * 7
+    L.nonode_sim_tiled_shape.argtypes = [ctypes.POINTER(_i)] * 2
+    L.nonode_sim_tiled_workspace_bytes.argtypes = [_i, _i]
+    L.nonode_sim_tiled_workspace_bytes.restype = _sz
+    L.nonode_sim_gravity_tiled.argtypes = [_i] * 4 + [_d] * 3 + [_vp] * 7 + [_sz, _vp]
+    L.nonode_sim_charged_tiled.argtypes = [_i] * 4 + [_d] * 3 + [_vp] * 6 + [_sz, _vp]
     L.nonode_gather_batch.argtypes = [_i] * 6 + [_vp] * 13
     L.nonode_gather_rows.argtypes = [_i, ctypes.c_longlong, _i, _vp, _vp, _vp, _vp]
     L.nonode_rollout_metrics.argtypes = [_i] * 3 + [_vp] * 5

@@ -4,8 +4,9 @@
 Initial conditions are drawn on the host with numpy in exactly the reference's call order
 (np.random.choice / randn per simulation, then the observation-noise draws), so a given
 np.random.seed reproduces the reference's datasets; the time integration runs in one kernel launch
-for every trajectory of a batch (csrc/nonode_sim.hip, float64). Outputs are numpy arrays in the
-reference's shapes; ``device=`` variants keep the trajectories on the GPU.
+for every trajectory of a batch up to 1024 bodies, and in one launch per step of tiled
+multi-workgroup kernels above that (csrc/nonode_sim.hip, float64; ``kernel=`` chooses). Outputs are
+numpy arrays in the reference's shapes; ``as_numpy=False`` keeps the trajectories on the GPU.
 """
 import os
 
@@ -19,6 +20,30 @@ def _dev_f64(a, device):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
 
 
+RESIDENT_NMAX = 1024   # nonode_sim_gravity / nonode_sim_charged: one workgroup holds a trajectory
+
+
+def _pick_kernel(kernel, n):
+    """The simulator kernel for n bodies: "resident" (one workgroup per trajectory, n <= 1024) or "tiled"
+    (receiver tiles, one launch per step, any n). None keeps the resident kernel wherever it serves."""
+    if kernel is None:
+        return "resident" if n <= RESIDENT_NMAX else "tiled"
+    if kernel not in ("resident", "tiled"):
+        raise ValueError(f"kernel must be None, 'resident' or 'tiled', not {kernel!r}")
+    if kernel == "resident" and n > RESIDENT_NMAX:
+        raise ValueError(f"kernel='resident' holds a trajectory in one workgroup: n_balls <= {RESIDENT_NMAX}, "
+                         f"not {n} (use kernel='tiled' or None)")
+    return kernel
+
+
+def _tiled_workspace(S, n, dev):
+    nbytes = _lib.lib().nonode_sim_tiled_workspace_bytes(S, n)
+    if nbytes == 0:
+        raise ValueError(f"the tiled simulators take n_balls <= 2**20 and S * n_balls < 2**31, not S={S}, "
+                         f"n_balls={n}")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=dev), nbytes
+
+
 def _default_device():
     if not torch.cuda.is_available():
         raise _lib.NonodeError("no CPU path: the simulators run on a ROCm GPU (the CPU restatement is "
@@ -27,7 +52,13 @@ def _default_device():
 
 
 class ChargedParticlesSim:
-    """synthetic_sim.py:149-296 (charged particles, leapfrog with clamped Coulomb forces)."""
+    """synthetic_sim.py:149-296 (charged particles, leapfrog with clamped Coulomb forces).
+
+    Any n_balls up to 2**20 (S * n_balls < 2**31): up to 1024 one workgroup integrates a trajectory in one
+    launch, above that the tiled kernel runs one launch per step (``kernel=``). The initial positions are
+    drawn with loc_std * (n_balls / 5) ** (1/3) and must lie within 3 * box_size, as in the reference: the
+    default box_size = 5 does not hold a large system (at n_balls = 1100 the largest draw is about 25), so
+    pass a box_size that does."""
 
     def __init__(self, n_balls=5, box_size=5., loc_std=1., vel_norm=0.5, interaction_strength=1., noise_var=0.):
         self.n_balls = n_balls
@@ -62,10 +93,14 @@ class ChargedParticlesSim:
         return charges, loc, vel
 
     def sample_trajectories(self, S, T=10000, sample_freq=10, charge_prob=(1. / 2, 0, 1. / 2), device=None,
-                            as_numpy=True):
-        """S consecutive sample_trajectory calls (the reference's RNG order) integrated in ONE launch.
-        Returns loc, vel [S, T_save, 3, N], edges [S, N, N], charges [S, N, 1]."""
+                            as_numpy=True, kernel=None, with_edges=True):
+        """S consecutive sample_trajectory calls (the reference's RNG order) integrated together (one launch
+        with the resident kernel, one per step with the tiled one; ``kernel`` as in integrate).
+        Returns loc, vel [S, T_save, 3, N], edges [S, N, N], charges [S, N, 1]. edges = q q^T is float64 on
+        the host, 8 N^2 bytes per trajectory (3.2 GB at N = 20,000): with_edges=False returns None in its
+        place and never forms it."""
         assert T % sample_freq == 0
+        _pick_kernel(kernel, self.n_balls)
         n, T_save = self.n_balls, T // sample_freq - 1
         q, l0, v0, noise = [], [], [], []
         for _ in range(S):
@@ -76,37 +111,45 @@ class ChargedParticlesSim:
         dev = torch.device(device) if device is not None else _default_device()
         _lib.require_device(torch.empty(0, device=dev))
         ql, ld, vd = _dev_f64(q.reshape(S, n), dev), _dev_f64(l0, dev), _dev_f64(v0, dev)
-        loc_d, vel_d = self.integrate(ql, ld, vd, T, sample_freq)
+        loc_d, vel_d = self.integrate(ql, ld, vd, T, sample_freq, kernel=kernel)
         if self.noise_var:
             loc_d += _dev_f64(np.stack([a for a, _ in noise]), dev) * self.noise_var
             vel_d += _dev_f64(np.stack([b for _, b in noise]), dev) * self.noise_var
-        edges = q @ np.transpose(q, (0, 2, 1))
+        edges = q @ np.transpose(q, (0, 2, 1)) if with_edges else None
         if not as_numpy:
             return loc_d, vel_d, edges, q
         return loc_d.cpu().numpy(), vel_d.cpu().numpy(), edges, q
 
-    def integrate(self, q, loc0, vel0, T, sample_freq):
+    def integrate(self, q, loc0, vel0, T, sample_freq, kernel=None):
         """The time integration of synthetic_sim.py:241-296 for S trajectories already on the GPU:
-        q [S, N], loc0 / vel0 [S, 3, N] float64 (after _clamp) -> loc, vel [S, T_save, 3, N], one
-        launch."""
-        _lib.require_device(q, loc0, vel0)
+        q [S, N], loc0 / vel0 [S, 3, N] float64 (after _clamp) -> loc, vel [S, T_save, 3, N].
+        kernel: None (the resident kernel, one launch, when N <= 1024, else the tiled one, one launch per
+        step), "tiled" (at any N; the same bits as the resident kernel where both run) or "resident"
+        (ValueError when N > 1024)."""
         S, n = q.shape
+        kernel = _pick_kernel(kernel, n)
+        _lib.require_device(q, loc0, vel0)
         T_save = T // sample_freq - 1
         loc_d = torch.empty(S, T_save, 3, n, dtype=torch.float64, device=q.device)
         vel_d = torch.empty_like(loc_d)
-        _lib.check(_lib.lib().nonode_sim_charged(S, n, T, sample_freq, self._delta_T, self._max_F,
-                                                 float(self.interaction_strength), _lib.ptr(loc0), _lib.ptr(vel0),
-                                                 _lib.ptr(q), _lib.ptr(loc_d), _lib.ptr(vel_d), _lib.stream_of(q)))
+        args = (S, n, T, sample_freq, self._delta_T, self._max_F, float(self.interaction_strength), _lib.ptr(loc0),
+                _lib.ptr(vel0), _lib.ptr(q), _lib.ptr(loc_d), _lib.ptr(vel_d))
+        if kernel == "resident":
+            _lib.check(_lib.lib().nonode_sim_charged(*args, _lib.stream_of(q)))
+        else:
+            ws, nbytes = _tiled_workspace(S, n, q.device)
+            _lib.check(_lib.lib().nonode_sim_charged_tiled(*args, _lib.ptr(ws), nbytes, _lib.stream_of(q)))
         return loc_d, vel_d
 
-    def sample_trajectory(self, T=10000, sample_freq=10, charge_prob=(1. / 2, 0, 1. / 2)):
+    def sample_trajectory(self, T=10000, sample_freq=10, charge_prob=(1. / 2, 0, 1. / 2), kernel=None):
         """synthetic_sim.py:220-296: loc, vel [T_save, 3, N], edges [N, N], charges [N, 1]."""
-        loc, vel, edges, q = self.sample_trajectories(1, T, sample_freq, charge_prob)
+        loc, vel, edges, q = self.sample_trajectories(1, T, sample_freq, charge_prob, kernel=kernel)
         return loc[0], vel[0], edges[0], q[0]
 
 
 class GravitySim:
-    """synthetic_sim.py:299-481 (softened gravity, kick-drift-kick)."""
+    """synthetic_sim.py:299-481 (softened gravity, kick-drift-kick). Any n_balls up to 2**20
+    (batch_size * n_balls < 2**31); above 1024 the tiled kernel runs one launch per step (``kernel=``)."""
 
     def __init__(self, n_balls=100, loc_std=1, vel_norm=0.5, interaction_strength=1, noise_var=0, dt=0.001,
                  softening=0.1):
@@ -119,10 +162,16 @@ class GravitySim:
         self.softening = softening
         self.dim = 3
 
-    def sample_trajectory_batch(self, T=10000, sample_freq=10, batch_size=1, device=None, as_numpy=True):
-        """synthetic_sim.py:407-456: pos, vel, force [B, T_save, N, 3], mass [B, N, 1]."""
+    def sample_trajectory_batch(self, T=10000, sample_freq=10, batch_size=1, device=None, as_numpy=True,
+                                kernel=None):
+        """synthetic_sim.py:407-456: pos, vel, force [B, T_save, N, 3], mass [B, N, 1] (device tensors with
+        as_numpy=False; mass stays the host array it was drawn as).
+        kernel: None (the resident kernel, one launch, when N <= 1024, else the tiled one, one launch per
+        step), "tiled" (at any N; the same bits as the resident kernel where both run) or "resident"
+        (ValueError when N > 1024)."""
         assert T % sample_freq == 0
         T_save, N = T // sample_freq, self.n_balls
+        kernel = _pick_kernel(kernel, N)
         mass = np.ones((batch_size, N, 1))
         mass += np.random.randn(batch_size, N, 1) * self.loc_std * 0.1
         pos = np.random.randn(batch_size, N, self.dim)
@@ -134,10 +183,13 @@ class GravitySim:
         _lib.require_device(torch.empty(0, device=dev))
         out = [torch.empty(batch_size, T_save, N, 3, dtype=torch.float64, device=dev) for _ in range(3)]
         pd, vd, md = _dev_f64(pos, dev), _dev_f64(vel, dev), _dev_f64(mass.reshape(batch_size, N), dev)
-        _lib.check(_lib.lib().nonode_sim_gravity(batch_size, N, T, sample_freq, float(self.dt),
-                                                 float(self.interaction_strength), float(self.softening),
-                                                 _lib.ptr(pd), _lib.ptr(vd), _lib.ptr(md), *[_lib.ptr(t) for t in out],
-                                                 _lib.stream_of(pd)))
+        args = (batch_size, N, T, sample_freq, float(self.dt), float(self.interaction_strength),
+                float(self.softening), _lib.ptr(pd), _lib.ptr(vd), _lib.ptr(md), *[_lib.ptr(t) for t in out])
+        if kernel == "resident":
+            _lib.check(_lib.lib().nonode_sim_gravity(*args, _lib.stream_of(pd)))
+        else:
+            ws, nbytes = _tiled_workspace(batch_size, N, dev)
+            _lib.check(_lib.lib().nonode_sim_gravity_tiled(*args, _lib.ptr(ws), nbytes, _lib.stream_of(pd)))
         if self.noise_var:
             for t, z in zip(out, noise):
                 t += _dev_f64(z, dev) * self.noise_var
@@ -145,22 +197,23 @@ class GravitySim:
             return out[0], out[1], out[2], mass
         return out[0].cpu().numpy(), out[1].cpu().numpy(), out[2].cpu().numpy(), mass
 
-    def sample_trajectory(self, T=10000, sample_freq=10):
+    def sample_trajectory(self, T=10000, sample_freq=10, kernel=None):
         """synthetic_sim.py:360-404 (the single-trajectory form; its RNG draws differ from the batch
         form only in shape): pos, vel, force [T_save, N, 3], mass [N, 1]."""
-        pos, vel, force, mass = self.sample_trajectory_batch(T, sample_freq, 1)
+        pos, vel, force, mass = self.sample_trajectory_batch(T, sample_freq, 1, kernel=kernel)
         return pos[0], vel[0], force[0], mass[0]
 
 
-def generate_dataset(sim, num_sims, length, sample_freq):
+def generate_dataset(sim, num_sims, length, sample_freq, kernel=None):
     """generate_dataset.py:62-104: gravity in batches of 50 (sample_trajectory_batch), charged one
-    simulation at a time in the reference; here every charged simulation of the split is one
-    launch (same RNG order). Returns loc, vel, edges, charges as the reference stacks them."""
+    simulation at a time in the reference; here every charged simulation of the split is integrated
+    together (same RNG order). Returns loc, vel, edges, charges as the reference stacks them.
+    kernel: passed to the simulator (None, "resident" or "tiled")."""
     if isinstance(sim, GravitySim):
-        parts = [sim.sample_trajectory_batch(T=length, sample_freq=sample_freq, batch_size=50)
+        parts = [sim.sample_trajectory_batch(T=length, sample_freq=sample_freq, batch_size=50, kernel=kernel)
                  for _ in range(num_sims // 50 + (num_sims % 50 > 0))]
         return tuple(np.concatenate([p[k] for p in parts], axis=0) for k in range(4))
-    return sim.sample_trajectories(num_sims, T=length, sample_freq=sample_freq)
+    return sim.sample_trajectories(num_sims, T=length, sample_freq=sample_freq, kernel=kernel)
 
 
 def dataset_suffix(simulation, n_balls, initial_vel=1, suffix=""):
