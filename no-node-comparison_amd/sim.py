@@ -44,6 +44,31 @@ def _tiled_workspace(S, n, dev):
     return torch.empty(nbytes // 8, dtype=torch.float64, device=dev), nbytes
 
 
+def _check_state(who, T, sample_freq, main, others):
+    """The host checks of an integrate(): every argument a float64 tensor of its stated shape, all on one
+    device, sample_freq dividing T. main = (name, tensor, shape words) fixes S and N; others = [(name, tensor,
+    shape given S and N, shape words)]. Raises TypeError / ValueError naming the argument; returns the tensors
+    made contiguous. No device work: a CPU tensor passes (require_device refuses it afterwards)."""
+    name, t, words = main
+    for nm, a in [(name, t)] + [(o[0], o[1]) for o in others]:
+        if not isinstance(a, torch.Tensor):
+            raise TypeError(f"{who}: {nm} must be a torch.Tensor, not {type(a).__name__}")
+        if a.dtype != torch.float64:
+            raise TypeError(f"{who}: {nm} must be float64, not {a.dtype}")
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{who}: {name} must have shape {words}, not {tuple(t.shape)}")
+    S, n = t.shape
+    for nm, a, shape, w in others:
+        if tuple(a.shape) != shape(S, n):
+            raise ValueError(f"{who}: {nm} must have shape {w} = {shape(S, n)} (from {name} {tuple(t.shape)}), "
+                             f"not {tuple(a.shape)}")
+        if a.device != t.device:
+            raise ValueError(f"{who}: {nm} is on {a.device}, {name} on {t.device}: one device for all")
+    if int(T) != T or int(sample_freq) != sample_freq or T <= 0 or sample_freq <= 0 or T % sample_freq:
+        raise ValueError(f"{who}: T={T} sample_freq={sample_freq} (positive integers, sample_freq divides T)")
+    return [t.contiguous()] + [o[1].contiguous() for o in others]
+
+
 def _default_device():
     if not torch.cuda.is_available():
         raise _lib.NonodeError("no CPU path: the simulators run on a ROCm GPU (the CPU restatement is "
@@ -126,12 +151,17 @@ class ChargedParticlesSim:
         kernel: None (the resident kernel, one launch, when N <= 1024, else the tiled one, one launch per
         step), "tiled" (at any N; the same bits as the resident kernel where both run) or "resident"
         (ValueError when N > 1024)."""
+        q, loc0, vel0 = _check_state("ChargedParticlesSim.integrate", T, sample_freq, ("q", q, "[S, N]"),
+                                     [("loc0", loc0, lambda S, n: (S, 3, n), "[S, 3, N]"),
+                                      ("vel0", vel0, lambda S, n: (S, 3, n), "[S, 3, N]")])
         S, n = q.shape
         kernel = _pick_kernel(kernel, n)
         _lib.require_device(q, loc0, vel0)
         T_save = T // sample_freq - 1
         loc_d = torch.empty(S, T_save, 3, n, dtype=torch.float64, device=q.device)
         vel_d = torch.empty_like(loc_d)
+        if T_save == 0:   # T == sample_freq: the reference returns empty arrays; nothing to launch
+            return loc_d, vel_d
         args = (S, n, T, sample_freq, self._delta_T, self._max_F, float(self.interaction_strength), _lib.ptr(loc0),
                 _lib.ptr(vel0), _lib.ptr(q), _lib.ptr(loc_d), _lib.ptr(vel_d))
         if kernel == "resident":
@@ -181,21 +211,35 @@ class GravitySim:
         noise = [np.random.randn(batch_size, T_save, N, self.dim) for _ in range(3)]
         dev = torch.device(device) if device is not None else _default_device()
         _lib.require_device(torch.empty(0, device=dev))
-        out = [torch.empty(batch_size, T_save, N, 3, dtype=torch.float64, device=dev) for _ in range(3)]
         pd, vd, md = _dev_f64(pos, dev), _dev_f64(vel, dev), _dev_f64(mass.reshape(batch_size, N), dev)
-        args = (batch_size, N, T, sample_freq, float(self.dt), float(self.interaction_strength),
-                float(self.softening), _lib.ptr(pd), _lib.ptr(vd), _lib.ptr(md), *[_lib.ptr(t) for t in out])
-        if kernel == "resident":
-            _lib.check(_lib.lib().nonode_sim_gravity(*args, _lib.stream_of(pd)))
-        else:
-            ws, nbytes = _tiled_workspace(batch_size, N, dev)
-            _lib.check(_lib.lib().nonode_sim_gravity_tiled(*args, _lib.ptr(ws), nbytes, _lib.stream_of(pd)))
+        out = self.integrate(pd, vd, md, T, sample_freq, kernel=kernel)
         if self.noise_var:
             for t, z in zip(out, noise):
                 t += _dev_f64(z, dev) * self.noise_var
         if not as_numpy:
             return out[0], out[1], out[2], mass
         return out[0].cpu().numpy(), out[1].cpu().numpy(), out[2].cpu().numpy(), mass
+
+    def integrate(self, pos0, vel0, mass, T, sample_freq, kernel=None):
+        """The time integration of synthetic_sim.py:435-450 for B trajectories already on the GPU:
+        pos0 / vel0 [B, N, 3], mass [B, N] float64 -> pos, vel, force [B, T_save, N, 3], T_save = T / sample_freq.
+        kernel as in sample_trajectory_batch."""
+        mass, pos0, vel0 = _check_state("GravitySim.integrate", T, sample_freq, ("mass", mass, "[B, N]"),
+                                        [("pos0", pos0, lambda B, n: (B, n, 3), "[B, N, 3]"),
+                                         ("vel0", vel0, lambda B, n: (B, n, 3), "[B, N, 3]")])
+        B, N = mass.shape
+        kernel = _pick_kernel(kernel, N)
+        _lib.require_device(pos0, vel0, mass)
+        T_save = T // sample_freq
+        out = [torch.empty(B, T_save, N, 3, dtype=torch.float64, device=mass.device) for _ in range(3)]
+        args = (B, N, T, sample_freq, float(self.dt), float(self.interaction_strength), float(self.softening),
+                _lib.ptr(pos0), _lib.ptr(vel0), _lib.ptr(mass), *[_lib.ptr(t) for t in out])
+        if kernel == "resident":
+            _lib.check(_lib.lib().nonode_sim_gravity(*args, _lib.stream_of(mass)))
+        else:
+            ws, nbytes = _tiled_workspace(B, N, mass.device)
+            _lib.check(_lib.lib().nonode_sim_gravity_tiled(*args, _lib.ptr(ws), nbytes, _lib.stream_of(mass)))
+        return out[0], out[1], out[2]
 
     def sample_trajectory(self, T=10000, sample_freq=10, kernel=None):
         """synthetic_sim.py:360-404 (the single-trajectory form; its RNG draws differ from the batch

@@ -7,15 +7,17 @@ from oracle import sim as osim
 from tests.conftest import load_golden
 
 
-def charged_initial_states(seed, n, sims, T, freq, loc_std=1.0, vel_norm=0.5, box=5.0):
+def charged_initial_states(seed, n, sims, T, freq, loc_std=1.0, vel_norm=0.5, box=5.0, charge_prob=(0.5, 0, 0.5),
+                           with_noise=False):
     """Replays the reference's RNG draws for `sims` consecutive sample_trajectory calls
-    (synthetic_sim.py:224-238, generate_dataset.py:56) and returns the clamped initial states."""
+    (synthetic_sim.py:224-238, generate_dataset.py:56) and returns the clamped initial states (q, loc, vel);
+    with_noise=True appends each simulation's two observation-noise draws: (q, loc, vel, z_loc, z_vel)."""
     np.random.seed(seed)
     std = loc_std * (float(n) / 5.) ** (1 / 3)
     out = []
     T_save = T // freq - 1
     for _ in range(sims):
-        q = np.random.choice(np.array([-1., 0., 1.]), size=(n, 1), p=[0.5, 0, 0.5])
+        q = np.random.choice(np.array([-1., 0., 1.]), size=(n, 1), p=list(charge_prob))
         loc = np.random.randn(3, n) * std
         vel = np.random.randn(3, n)
         vel = vel * vel_norm / np.sqrt((vel ** 2).sum(axis=0)).reshape(1, -1)
@@ -25,9 +27,8 @@ def charged_initial_states(seed, n, sims, T, freq, loc_std=1.0, vel_norm=0.5, bo
         under = loc < -box
         loc[under] = -2 * box - loc[under]
         vel[under] = np.abs(vel[under])
-        np.random.randn(T_save, 3, n)
-        np.random.randn(T_save, 3, n)      # the (zero-variance) observation noise draws
-        out.append((q, loc, vel))
+        z = (np.random.randn(T_save, 3, n), np.random.randn(T_save, 3, n))   # the observation noise draws
+        out.append((q, loc, vel) + (z if with_noise else ()))
     return out
 
 
